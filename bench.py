@@ -12,10 +12,15 @@ visible.  Under torchrun (RANK set) each rank runs its shard: scenarios are shar
 for cfg3), one RCCL all-reduce of the flat gradient per step.  Rank 0 prints ONE JSON line.  Inputs (demand traces from the
 HIP Philox sampler, initial state, weights) are resident in HBM before the timed region.
 
-The JSON line carries `roofline` for the kernel class with the largest total time in the step (its name is what the C ABI
-reported launching, `nic_last_kernel()`; `bound` is "mfma" for the 512-wide policy GEMMs and "hbm" for everything else,
-with the algorithmic bytes / flops per launch defined in `algorithmic_work`), `kernels` with the same figures for every
-class, `roofline_env_step` for the env-step kernel, and `cpu_baseline` (the oracle timed on this host's cores).
+A plain run sets up, warms up, times the K steps (`ms_per_step`: milliseconds per timed step) and prints the line.
+`--dump-outputs DIR` also writes what the last timed step computed (its scalars, the parameters and gradients it left) as
+DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+With `--full` the JSON line also carries `roofline` for the kernel class with the largest total time in the step (its name is
+what the C ABI reported launching, `nic_last_kernel()`; `bound` is "mfma" for the 512-wide policy GEMMs and "hbm" for
+everything else, with the algorithmic bytes / flops per launch defined in `algorithmic_work`), `kernels` with the same
+figures for every class, `roofline_env_step` for the env-step kernel, the collective's time, and `cpu_baseline` (the oracle
+timed on this host's cores); epoch workloads add their launch-mode and data-loader variants.
 """
 import argparse
 import json
@@ -80,6 +85,37 @@ def _emit(out):
     f = _REAL_STDOUT or sys.stdout
     f.write(json.dumps(out) + "\n")
     f.flush()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(model, **scalars):
+    """What a caller of the timed step holds after its last run: the step's scalars (float64) and, per parameter, the value the
+    optimizer left and the gradient it stepped with (float32), copied to the host right after the timed region."""
+    out = {k: torch.tensor(float(v), dtype=torch.float64) for k, v in scalars.items()}
+    for name, p in model.named_parameters():
+        if isinstance(p, torch.nn.parameter.UninitializedParameter):
+            continue
+        out[f"param.{name}"] = p.detach().float().cpu()
+        if p.grad is not None:
+            out[f"grad.{name}"] = p.grad.detach().float().cpu()
+    return out
+
+
+def dump_outputs(directory, outputs):
+    """--dump-outputs: one DIR/<name>.npy per array.  Above DUMP_LIMIT_BYTES in all, every array larger than its share is replaced
+    by a fixed sample of its flattened entries (seed 0, the same indices in every run of the same shapes)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    total = sum(v.numel() * v.element_size() for v in outputs.values())
+    share = DUMP_LIMIT_BYTES // max(len(outputs), 1)
+    for name, v in outputs.items():
+        a = v.numpy()
+        if total > DUMP_LIMIT_BYTES and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def _lib_id():
@@ -516,6 +552,8 @@ def bench_epoch(args):
         tmax = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         dt = float(tmax)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(model, train_loss_per_store_period=last[0], reported_loss_per_store_period=last[1]))
     if rank != 0:
         return
     n_samples = len(loaders["train"].dataset)
@@ -659,10 +697,19 @@ def main():
                     help="data_driven workloads: the per-period kernels instead of the whole-horizon kernels (A/B)")
     ap.add_argument("--horizon-max-scenarios", type=int, default=0,
                     help="data_driven workloads: largest batch that takes the whole-horizon kernels (default: the engine's 8192)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what stands beside the headline figure: per-kernel timings and rooflines, the sampler, the "
+                         "collective's time, the epoch variants and the CPU baseline (default: set-up, warm-up, the timed steps and "
+                         "the result line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (its scalars, and the parameters and "
+                         "gradients it left) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
+    if not args.full:
+        args.no_cpu_baseline = args.no_kernel_timing = True
 
     _quiet_stdout()
     from neural_inventory_control_amd import workloads as _w
@@ -841,7 +888,7 @@ def main():
         stride = args.timing_stride or (1 if whole else (10 if gnn else 40))
         timer = eng.timer = KernelTimer(stride=stride)
     if reducer is not None:
-        reducer.timing, reducer._events, reducer.calls = True, [], 0
+        reducer.timing, reducer._events, reducer.calls = args.full, [], 0
     if sharded:
         torch.distributed.barrier()
     torch.cuda.synchronize()
@@ -857,6 +904,8 @@ def main():
         tmax = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         dt = float(tmax)
+    if args.dump_outputs and rank == 0:   # (before the kernel-timing passes below run the engine again)
+        dump_outputs(args.dump_outputs, step_outputs(model, total_cost=last))
     timer_steps = args.steps
     if closed_form_replay and not getattr(args, "no_kernel_timing_flag", False):
         # the whole-horizon kernel of the replayed step, timed in eager launches of the same engine on the same batch

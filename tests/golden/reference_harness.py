@@ -1,10 +1,9 @@
 """Import harness for the upstream reference (THIS CONTAINER ONLY).
 
-The reference lives read-only at /root/reference and is never copied into this
-repo nor shipped to the GPU box.  This module makes `import trainer` etc. work
-so that golden vectors can be generated (make_golden.py) and the oracle can be
-pinned bit-for-bit against it (tests/test_oracle_vs_reference.py, skipped when
-/root/reference is absent).
+The reference tree (NIC_REFERENCE_ROOT) is read-only and is never copied into
+this repo.  This module makes `import trainer` etc. work so that the golden
+vectors and the reference pins the tests compare against can be generated
+(make_golden.py, make_reference_pins.py).
 
 gymnasium is not installed in the image; the reference only uses
 `gym.Env`, `spaces.Box`, `spaces.Dict` (environment.py:7,21-22,352-358,380-389)

@@ -66,6 +66,51 @@ class Golden:
 ZERO_LEAD_CASES = {"f1_many_warehouses_2x10_gnn"}
 
 
+def tensor_digest(t):
+    """dtype, shape and sha256 of a tensor's bytes: equal digests <=> bit-equal tensors (what a fixture stores instead of a
+    tensor the test regenerates and compares with torch.equal)."""
+    import hashlib
+    a = t.detach().cpu().contiguous().numpy() if torch.is_tensor(t) else np.ascontiguousarray(t)
+    return f"{a.dtype}{list(a.shape)}:{hashlib.sha256(a.tobytes()).hexdigest()}"
+
+
+_DATA_ROOT = None
+
+
+def reference_data_root():
+    """A directory holding `data_files/...` as the reference ships them (the Favorita weekly sales, time and sample features,
+    per-series cost and lead-time tensors), rebuilt once per process from tests/golden/reference_data.npz.  The settings hold
+    paths relative to it, so the real-data cases run with it as the working directory."""
+    global _DATA_ROOT
+    if _DATA_ROOT is None:
+        import tempfile
+        z = np.load(os.path.join(GOLDEN_DIR, "reference_data.npz"), allow_pickle=False)
+        root = tempfile.mkdtemp(prefix="nic_reference_data_")
+        for key in z.files:
+            kind, rel = key.split("/", 1)
+            if kind == "dtype":
+                continue
+            path = os.path.join(root, "data_files", rel)
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            if kind == "file":
+                with open(path, "wb") as f:
+                    f.write(z[key].tobytes())
+            else:   # a tensor file, stored in the smallest exact dtype
+                torch.save(torch.from_numpy(z[key]).to(getattr(torch, str(z["dtype/" + rel]))), path)
+        _DATA_ROOT = root
+    return _DATA_ROOT
+
+
+def derived_one_store_file(rows_from=0):
+    """The one-store real-data blob the reference does not ship, derived as the fixtures were: every (product, store) series of
+    the 21-store weekly sales becomes a one-store sample (series `rows_from`.. of them); returns the path of a temp file."""
+    import tempfile
+    src = torch.load(os.path.join(reference_data_root(), "data_files/favorita_21_stores/weekly_sales.pt"), map_location="cpu")
+    path = os.path.join(tempfile.mkdtemp(), "one.pt")
+    torch.save(src.reshape(-1, 1, src.shape[2])[rows_from:].clone(), path)
+    return path
+
+
 def case_names():
     from cases import CASES
     return list(CASES.keys())

@@ -94,7 +94,7 @@ def test_bench_line_contract(workload):
     small = {"cfg3": ["--scenarios", "4096", "--periods", "10"], "cfg2": ["--scenarios", "8192", "--periods", "20"],
              "base_stock": ["--scenarios", "8192", "--periods", "20"]}[workload]
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", workload, "--steps", "2", "--warmup", "1",
-                        "--cpu-sample", "256"] + small, capture_output=True, text=True, timeout=900, cwd=root)
+                        "--full", "--cpu-sample", "256"] + small, capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -114,6 +114,31 @@ def test_bench_line_contract(workload):
     cb = out["cpu_baseline"]
     assert cb["kind"] == "port" and cb["value"] > 0 and cb["cores"] >= 1 and cb["host_cores"] >= cb["cores"] and "sample" in cb
     assert cb["unit"] == out["unit"]
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `bench.py` run (no --full) prints the headline line without the figures --full adds, and --dump-outputs writes
+    what the last timed step left: its total cost (the line's mean cost x the cost units) and every parameter and gradient."""
+    import numpy as np
+    root = os.path.dirname(HERE)
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg3", "--scenarios", "4096", "--periods", "10",
+           "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["dtype"] == "f32" and out["higher_is_better"] is True
+    assert not {"roofline", "kernels", "cpu_baseline"} & set(out)
+    cfg = out["config"]
+    total = float(np.load(tmp_path / "total_cost.npy"))
+    assert abs(total - cfg["mean_cost_per_store_period"] * cfg["global_scenarios"] * cfg["stores"] * cfg["periods"]) <= 1e-6 * abs(total)
+    files = {p.name: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    params = [k for k in files if k.startswith("param.")]
+    assert params and all("grad." + k[len("param."):] in files for k in params)
+    assert all(np.isfinite(a).all() for a in files.values())
 
 
 def test_bench_strong_and_weak_scaling_over_ranks_sharing_the_gpu():
@@ -152,7 +177,8 @@ def test_bench_epoch_workload_line():
     1,024 x 50 periods).  One JSON line with the driver's keys; a step is one batch; the epoch is also reported eager / replayed
     and with the reference-style host DataLoader."""
     root = os.path.dirname(HERE)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg3_yaml", "--steps", "8", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg3_yaml", "--steps", "8", "--warmup", "1",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -179,7 +205,7 @@ def test_bench_real_data_epoch_workload_line():
     replayed) reported beside it."""
     root = os.path.dirname(HERE)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "real_data_yaml", "--steps", "4", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -201,7 +227,7 @@ def test_bench_one_store_real_data_quantile_epoch_workload_line():
     training steps replayed from a HIP graph; the reference-style loop (Simulator.step per period) reported beside it."""
     root = os.path.dirname(HERE)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "one_store_real_transformed_nv_yaml", "--steps", "4",
-                        "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
+                        "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -245,7 +271,7 @@ def test_bench_two_ranks_under_real_rccl_describes_its_collective():
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "cfg4", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     c = line["collective"]
@@ -263,7 +289,7 @@ def test_bench_single_rank_line_carries_the_collective_of_a_one_rank_rccl_group(
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg4", "--scenarios", "2048", "--periods", "10",
-                        "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+                        "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     c = line["collective"]

@@ -269,23 +269,17 @@ REAL_CASES = [n for n in case_names() if n.startswith("f4_real")]
 @pytest.mark.parametrize("name", REAL_CASES)
 def test_real_data_scenario_and_period_split_equal_reference(name):
     """`Scenario(periods=None)` on the shipped Favorita files + `DatasetCreator.split_by_period` reproduce the
-    reference's dataset dict (fixture `data/*`) bit for bit.  Needs the reference's data files (this container)."""
+    reference's dataset dict (fixture `data/*`) bit for bit, on the reference's data files (tests/golden/reference_data.npz)."""
     import os
-    import tempfile
+    from golden_io import derived_one_store_file, reference_data_root
     g = Golden(name)
     c = g.fresh_config()
-    ref_root = "/root/reference"
-    if not os.path.isdir(os.path.join(ref_root, "data_files")):
-        pytest.skip("the reference's data files are not on this machine")
     sp = c["store_params"]
     cwd = os.getcwd()
-    os.chdir(ref_root)
+    os.chdir(reference_data_root())
     try:
         if sp["demand"]["file_location"].startswith("<derived"):
-            src = torch.load("data_files/favorita_21_stores/weekly_sales.pt", map_location="cpu")
-            loc = os.path.join(tempfile.mkdtemp(), "one.pt")
-            torch.save(src.reshape(-1, 1, src.shape[2]).clone(), loc)
-            sp["demand"]["file_location"] = loc
+            sp["demand"]["file_location"] = derived_one_store_file()
         sc = Scenario(None, c["problem_params"], sp, c["warehouse_params"], c["echelon_params"], c["n"],
                       c["observation_params"], c["seeds"])
         (ds,) = DatasetCreator().create_datasets(sc, split=True, by_period=True, periods_for_split=[c["period_range"]])

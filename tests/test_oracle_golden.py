@@ -7,16 +7,13 @@ import numpy as np
 import pytest
 import torch
 
-from golden_io import Golden, case_names, check_slim_inputs, slim_case_names
+from golden_io import Golden, case_names, check_slim_inputs, derived_one_store_file, reference_data_root, slim_case_names
 from oracle import inventory_oracle as orc
-
-
-REF_ROOT = "/root/reference"
 
 
 def _build(g, need_data=True):
     """Config of a fixture and, for synthetic cases, the oracle's own scenario data.  Real-data cases read the
-    Favorita files the reference ships: their data is rebuilt only where /root/reference exists (this container)."""
+    Favorita files the reference ships (stored in tests/golden/reference_data.npz)."""
     import os
     c = g.fresh_config()
     if not c.get("real"):
@@ -25,19 +22,13 @@ def _build(g, need_data=True):
         return c, data
     if not need_data:
         return c, None
-    if not os.path.isdir(os.path.join(REF_ROOT, "data_files")):
-        pytest.skip("the reference's data files are not on this machine")
     sp = c["store_params"]
     loc = sp["demand"]["file_location"]
     cwd = os.getcwd()
-    os.chdir(REF_ROOT)  # the YAMLs hold paths relative to the reference root
+    os.chdir(reference_data_root())  # the YAMLs hold paths relative to the reference root
     try:
         if loc.startswith("<derived"):  # one-store blob derived from the shipped 21-store file (tests/golden/make_golden.py)
-            import tempfile
-            src = torch.load("data_files/favorita_21_stores/weekly_sales.pt", map_location="cpu")
-            loc = os.path.join(tempfile.mkdtemp(), "one.pt")
-            torch.save(src.reshape(-1, 1, src.shape[2]).clone(), loc)
-            sp["demand"]["file_location"] = loc
+            sp["demand"]["file_location"] = derived_one_store_file()
         full = orc.generate_scenario_data(None, c["problem_params"], sp, c["warehouse_params"], c["echelon_params"], c["n"],
                                           c["observation_params"], c["seeds"])
     finally:

@@ -174,12 +174,12 @@ def main():
         big = ("cfg3", "cfg5", "gnn", "gnn_many_warehouses", "cfg3_shard8")
         steps = (["--steps", "16", "--warmup", "1"] if w in epoch else
                  ["--steps", "3", "--warmup", "1"] if w in big else ["--steps", "20", "--warmup", "3"])
-        run(["python3", "bench.py", "--workload", w] + steps, os.path.join(out, f"{rnd}_bench_{w}.json"))
+        run(["python3", "bench.py", "--workload", w, "--full"] + steps, os.path.join(out, f"{rnd}_bench_{w}.json"))
         prof = os.path.join(out, "prof_" + w)
         psteps = (["--steps", "8", "--warmup", "1", "--no-kernel-timing"] if w in epoch else
                   ["--steps", "2", "--warmup", "1"] if w in big else ["--steps", "5", "--warmup", "2"])
         run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", prof, "--", "python3", "bench.py",
-             "--workload", w, "--no-cpu-baseline", "--no-dist-init"] + psteps, os.path.join(out, f"{rnd}_bench_{w}_under_rocprof.json"))
+             "--workload", w, "--full", "--no-cpu-baseline", "--no-dist-init"] + psteps, os.path.join(out, f"{rnd}_bench_{w}_under_rocprof.json"))
         traces = glob.glob(os.path.join(prof, "**", "*kernel_trace.csv"), recursive=True)
         if traces:
             stats_from_trace(traces[0], os.path.join(out, f"{rnd}_bench_{w}_kernel_stats.csv"),
@@ -189,10 +189,10 @@ def main():
         if w in ("cfg1", "cfg2", "cfg4", "base_stock", "base_stock_1m", "echelon_stock"):
             # sub-millisecond steps: the one-rank RCCL all-reduce the default line includes (5 - 7 launches) is 10 - 30 % of them;
             # the same step without a process group, for comparison with the rounds that had none
-            run(["python3", "bench.py", "--workload", w, "--no-dist-init", "--no-cpu-baseline"] + steps,
+            run(["python3", "bench.py", "--workload", w, "--full", "--no-dist-init", "--no-cpu-baseline"] + steps,
                 os.path.join(out, f"{rnd}_bench_{w}_no_collective.json"))
         if w in ("base_stock", "base_stock_1m", "echelon_stock"):   # replayed by default since round 6: the eager step beside it
-            run(["python3", "bench.py", "--workload", w, "--no-graph", "--no-cpu-baseline"] + steps,
+            run(["python3", "bench.py", "--workload", w, "--full", "--no-graph", "--no-cpu-baseline"] + steps,
                 os.path.join(out, f"{rnd}_bench_{w}_eager.json"))
         print(w, open(os.path.join(out, f"{rnd}_bench_{w}.json")).read()[:300], flush=True)
     if "cfg3" in workloads:   # counter traffic of the headline workload rides along (bench.py reads it from profiles/ next time)

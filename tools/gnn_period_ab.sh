@@ -5,7 +5,7 @@ mkdir -p $out
 python -m pytest tests/test_gpu_rollout.py -x -q -k "gnn" 2>&1 | tail -4
 python tools/gnn_period_probe.py --out $out/probe_train.json > $out/probe_train.log 2>&1
 python tools/gnn_period_probe.py --eval --out $out/probe_eval.json > $out/probe_eval.log 2>&1
-for m in on off; do python bench.py --workload gnn --steps 3 --warmup 2 --gnn-period $m > $out/bench_gnn_$m.json 2> $out/bench_gnn_$m.err; done
+for m in on off; do python bench.py --workload gnn --steps 3 --warmup 2 --full --gnn-period $m > $out/bench_gnn_$m.json 2> $out/bench_gnn_$m.err; done
 python - <<PY
 import json
 for f in ("probe_train", "probe_eval"):

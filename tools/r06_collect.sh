@@ -17,10 +17,10 @@ timeout 1500 python tools/collect_profiles.py r06 traffic:base_stock traffic:bas
     traffic:cfg4 traffic:cfg5 traffic:cfg3_shard8 traffic:real_data_driven >> $O/collect_traffic.log 2>&1
 cp $O/r06_traffic_*.json profiles/ 2>/dev/null
 for w in base_stock base_stock_1m echelon_stock cfg1 cfg2 cfg4 real_data_driven; do
-  timeout 300 python bench.py --workload $w --steps 20 --warmup 3 > $O/r06_bench_$w.json 2>/dev/null
+  timeout 300 python bench.py --full --workload $w --steps 20 --warmup 3 > $O/r06_bench_$w.json 2>/dev/null
 done
-timeout 300 python bench.py --workload cfg5 --steps 5 --warmup 2 > $O/r06_bench_cfg5.json 2>/dev/null
-timeout 300 python bench.py --workload cfg3_shard8 --steps 8 --warmup 2 > $O/r06_bench_cfg3_shard8.json 2>/dev/null
+timeout 300 python bench.py --full --workload cfg5 --steps 5 --warmup 2 > $O/r06_bench_cfg5.json 2>/dev/null
+timeout 300 python bench.py --full --workload cfg3_shard8 --steps 8 --warmup 2 > $O/r06_bench_cfg3_shard8.json 2>/dev/null
 for w in gnn gnn_many_warehouses; do
   timeout 300 python tools/gnn_period_bwd_probe.py --workload $w --periods 6 --out $O/r06_gnn_period_bwd_stamps_$w.json > $O/probe_final_$w.log 2>&1
   echo "probe $w rc $?"
@@ -28,13 +28,13 @@ done
 timeout 600 python tools/gnn_period_pmc.py $O/r06_gnn_period_pmc.json > $O/pmc.log 2>&1
 echo "pmc rc $?"
 for w in gnn gnn_many_warehouses; do   # same-box A/B: eager launches with the per-kernel timer; the per-MLP backward; round 5's route replayed
-  timeout 300 python bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-graph > $O/r06_bench_${w}_eager.json 2>/dev/null
-  timeout 300 python bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-graph --gnn-bwd off > $O/r06_bench_${w}_per_mlp_backward.json 2>/dev/null
-  timeout 300 python bench.py --workload $w --steps 5 --warmup 2 --no-cpu-baseline --graph --gnn-bwd off --gnn-period $( [ $w = gnn ] && echo on || echo off ) > $O/r06_bench_${w}_round5_route_replayed.json 2>/dev/null
+  timeout 300 python bench.py --full --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-graph > $O/r06_bench_${w}_eager.json 2>/dev/null
+  timeout 300 python bench.py --full --workload $w --steps 5 --warmup 2 --no-cpu-baseline --no-graph --gnn-bwd off > $O/r06_bench_${w}_per_mlp_backward.json 2>/dev/null
+  timeout 300 python bench.py --full --workload $w --steps 5 --warmup 2 --no-cpu-baseline --graph --gnn-bwd off --gnn-period $( [ $w = gnn ] && echo on || echo off ) > $O/r06_bench_${w}_round5_route_replayed.json 2>/dev/null
 done
-timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/r06_bench_cfg3_driver_cmd.json 2>/dev/null
+timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/r06_bench_cfg3_driver_cmd.json 2>/dev/null
 for w in cfg1 cfg2 cfg4 gnn gnn_many_warehouses; do
-  timeout 900 python bench.py --workload $w --eval --periods 5000 --steps 3 --warmup 1 --no-cpu-baseline > $O/r06_bench_${w}_eval_T5000.json 2> $O/eval_$w.err
+  timeout 900 python bench.py --full --workload $w --eval --periods 5000 --steps 3 --warmup 1 --no-cpu-baseline > $O/r06_bench_${w}_eval_T5000.json 2> $O/eval_$w.err
   echo "eval $w rc $?"; python tools/show_bench.py $O/r06_bench_${w}_eval_T5000.json | head -3
 done
 WL=echelon_stock bash tools/pmc_sq_probe.sh > $O/r06_sq_echelon_chain.txt 2>&1   # (SQ counters of the closed-form chain kernel)

@@ -4,7 +4,7 @@ out=${1:-gpurun_out/tail_sweep}
 mkdir -p $out
 for n in 1024 4096 8192 16384 32768 65536; do
   for tail in on off; do
-    timeout 300 python bench.py --workload cfg3 --scenarios $n --periods 20 --steps 4 --warmup 1 --no-cpu-baseline --tail $tail > $out/cfg3_${n}_$tail.json 2> $out/cfg3_${n}_$tail.err
+    timeout 300 python bench.py --workload cfg3 --scenarios $n --periods 20 --steps 4 --warmup 1 --full --no-cpu-baseline --tail $tail > $out/cfg3_${n}_$tail.json 2> $out/cfg3_${n}_$tail.err
     python - <<PY
 import json
 try:
