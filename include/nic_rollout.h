@@ -164,6 +164,32 @@ int nic_wgrad_periods_num_splits(int32_t N, int32_t K, int32_t n_scenarios, int3
 int nic_linear_wgrad_periods(const float* dY, const float* X, float* slab, int64_t lds, int32_t N, int32_t K,
                              int32_t n_scenarios, int32_t ldb, int32_t n_splits, int32_t n_periods,
                              int64_t period_stride_dy, int64_t period_stride_x, void* stream);
+/* ---- opt-in bf16 GEMMs of the wide hidden layers (csrc/linear_bf16.hip; FusedRollout.gemm_precision = "bf16") ---------
+ * OUTSIDE the 1e-5 parity contract the FP32 entry points above keep: the contraction's operands are rounded to bf16 (round to
+ * nearest even) on the way into the matrix cores (v_mfma_f32_32x32x16_bf16); products, accumulation, bias, ELU and ELU' are FP32.
+ * Replace, for the hidden-to-hidden layers of the policy MLP (neural_networks.py:80-106; input = an ELU activation), the same
+ * reference lines as their FP32 siblings.  Weights are passed as bf16 bit patterns (uint16_t) that the caller keeps, 16-byte
+ * aligned rows (ld a multiple of 8); activations stay FP32 feature-major [rows][ldb] as for the FP32 kernels, ldb % 4 == 0.
+ * Eligible shapes: N and K multiples of 32, both >= 128 (nic_linear_bf16_ok).  No atomics: results are identical run to run. */
+int nic_linear_bf16_ok(int32_t N, int32_t K);
+/* nic_linear_fwd in bf16:  Y[n][b] = act( sum_k W[n][k] * bf16(X[k][b]) + bias[n] ),  W: bf16 [N][ldw].  Writes columns
+ * b < round_up(n_scenarios, 4) like nic_linear_fwd. */
+int nic_linear_bf16_fwd(const uint16_t* W, int64_t ldw, const float* bias /* may be NULL */, const float* X, float* Y,
+                        int32_t N, int32_t K, int32_t n_scenarios, int32_t ldb, int32_t act, void* stream);
+/* nic_linear_dgrad in bf16:  dX[k][b] = (sum_n Wt[k][n] * bf16(dY[n][b])) * act'(Hprev[k][b])  (+ dX if accumulate),
+ * Wt: bf16 [K][ldwt] (W transposed). */
+int nic_linear_bf16_dgrad(const uint16_t* Wt, int64_t ldwt, const float* dY, const float* Hprev, float* dX, int32_t N,
+                          int32_t K, int32_t n_scenarios, int32_t ldb, int32_t act_prev, int32_t accumulate, void* stream);
+/* nic_linear_wgrad / nic_linear_wgrad_periods in bf16: slab[split][n][k] += sum_b bf16(dY[n][b]) * bf16(X[k][b]) for k < K and
+ * slab[split][n][K] += sum_b dY[n][b] (FP32).  The same slab format, split semantics and period order as the FP32 entry points,
+ * so nic_wgrad_reduce finishes them; any n_splits >= 1 is accepted (nic_wgrad_num_splits / nic_wgrad_periods_num_splits give
+ * counts that fill the chip; unused slots are left untouched). */
+int nic_linear_bf16_wgrad(const float* dY, const float* X, float* slab, int64_t lds, int32_t N, int32_t K,
+                          int32_t n_scenarios, int32_t ldb, int32_t n_splits, void* stream);
+int nic_linear_bf16_wgrad_periods(const float* dY, const float* X, float* slab, int64_t lds, int32_t N, int32_t K,
+                                  int32_t n_scenarios, int32_t ldb, int32_t n_splits, int32_t n_periods,
+                                  int64_t period_stride_dy, int64_t period_stride_x, void* stream);
+
 /* x[r][b] = rint(x[r][b]) (round half to even = torch.round) over rows x n_scenarios of a scenario-minor block: the
  * reference's discrete allocation `action.round()` (trainer.py:201-202) between the policy head and the env step. */
 int nic_round_orders(float* x, int32_t rows, int32_t n_scenarios, int32_t ldb, void* stream);

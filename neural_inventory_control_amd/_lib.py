@@ -172,6 +172,11 @@ PROTOTYPES = {
     "nic_wgrad_periods_num_splits": (C.c_int, [_i32, _i32, _i32, _i32]),
     "nic_linear_wgrad": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
     "nic_linear_wgrad_periods": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp]),
+    "nic_linear_bf16_ok": (C.c_int, [_i32, _i32]),
+    "nic_linear_bf16_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "nic_linear_bf16_dgrad": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "nic_linear_bf16_wgrad": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "nic_linear_bf16_wgrad_periods": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp]),
     "nic_linear_bwd_thin": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "nic_wgrad_reduce": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i32, _i32, _f32, _vp]),
     "nic_head_warehouse_fwd": (C.c_int, [_vp, _vp, _vp, _f32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -24,6 +24,7 @@ from .data_handling import DatasetCreator, DeviceBatches, Scenario
 from .environment import Simulator
 from .loss_functions import PolicyLoss
 from .neural_networks import NeuralNetworkCreator
+from .rollout import check_gemm_precision
 from .trainer import Trainer
 
 SETTING_KEYS = ("seeds", "test_seeds", "problem_params", "params_by_dataset", "observation_params", "store_params",
@@ -102,6 +103,8 @@ def build(config_setting, config_hyperparams, device, rank=0, world_size=1):
     trainer.use_step_graph = trainer_params.get("use_step_graph", "auto")   # true / false / "auto" (closed-form policies only)
     # ... and for the MLP engine's launch sequence: true / false / "auto" (default: decided by measurement, rollout.py)
     trainer.use_rollout_graph = trainer_params.get("use_rollout_graph", "auto")
+    # ... and the MLP engine's GEMM precision: "fp32" (default, the parity contract) or "bf16" (opt-in, rollout.py)
+    trainer.gemm_precision = check_gemm_precision(trainer_params.get("gemm_precision", "fp32"))
     trainer_params["base_dir"] = trainer_params.get("base_dir", "saved_models")
     trainer_params["save_model_folders"] = [trainer.get_year_month_day(), nn_params["name"]]
     trainer_params["save_model_filename"] = trainer.get_time_stamp()

@@ -134,6 +134,58 @@ def linear_wgrad_periods(dY, X, slab, n_scenarios):
     return slab
 
 
+# ---- opt-in bf16 GEMMs (csrc/linear_bf16.hip): outside the 1e-5 parity contract, see include/nic_rollout.h ---------------
+
+def linear_bf16_ok(N, K):
+    """shapes the bf16 GEMMs take: N and K multiples of 32, both >= 128"""
+    return bool(lib().nic_linear_bf16_ok(int(N), int(K)))
+
+
+def _bf16_weights(W):
+    if W.dtype != torch.bfloat16:
+        raise TypeError(f"bf16 GEMM weights must be torch.bfloat16 (got {W.dtype})")
+    return W
+
+
+def linear_bf16_fwd(W, bias, X, Y, n_scenarios, act):
+    """Y[N][ldb] = act(W[N][K(ldw)] @ bf16(X[K][ldb]) + bias), W a bf16 tensor; FP32 accumulation, bias and activation."""
+    _dev(X)
+    _bf16_weights(W)
+    N, K = W.shape[0], X.shape[0]
+    check(lib().nic_linear_bf16_fwd(ptr(W), _ld(W), ptr(bias), ptr(X), ptr(Y), N, K, n_scenarios, X.stride(0), act,
+                                    current_stream()))
+    return Y
+
+
+def linear_bf16_dgrad(Wt, dY, Hprev, dX, n_scenarios, act_prev, accumulate):
+    """dX[K][ldb] (+)= (Wt[K][N(ldwt)] @ bf16(dY[N][ldb])) * act'(Hprev), Wt a bf16 tensor."""
+    _dev(dY)
+    _bf16_weights(Wt)
+    K, N = dX.shape[0], dY.shape[0]
+    check(lib().nic_linear_bf16_dgrad(ptr(Wt), _ld(Wt), ptr(dY), ptr(Hprev), ptr(dX), N, K, n_scenarios, dY.stride(0),
+                                      act_prev, int(accumulate), current_stream()))
+    return dX
+
+
+def linear_bf16_wgrad(dY, X, slab, n_scenarios):
+    """slab[split][N][lds] += per-split sum_b bf16(dY[N][b]) bf16(X[K][b]) (column K = FP32 bias gradient)."""
+    _dev(dY)
+    N, K = dY.shape[0], X.shape[0]
+    check(lib().nic_linear_bf16_wgrad(ptr(dY), ptr(X), ptr(slab), slab.stride(1), N, K, n_scenarios, dY.stride(0),
+                                      slab.shape[0], current_stream()))
+    return slab
+
+
+def linear_bf16_wgrad_periods(dY, X, slab, n_scenarios):
+    """`linear_wgrad_periods` with bf16 operands: dY [T][N][ldb], X [T][K'][ldb] views, slab += sum_t per-split dY[t] X[t]^T."""
+    _dev(dY)
+    T, N, K = dY.shape[0], dY.shape[1], X.shape[1]
+    assert X.shape[0] == T and dY.stride(1) == X.stride(1) and dY.stride(2) == 1 and X.stride(2) == 1
+    check(lib().nic_linear_bf16_wgrad_periods(ptr(dY), ptr(X), ptr(slab), slab.stride(1), N, K, n_scenarios, dY.stride(1),
+                                              slab.shape[0], T, dY.stride(0), X.stride(0), current_stream()))
+    return slab
+
+
 def linear_bwd_thin_ok(N, K):
     """shapes nic_linear_bwd_thin takes (the logits layer of the policy MLPs)"""
     return N <= _lib.NIC_THIN_MAX_ROWS and K >= 32 and K % 32 == 0

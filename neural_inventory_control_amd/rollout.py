@@ -30,6 +30,17 @@ _HEADS = {"vanilla_one_store": "softplus", "vanilla_warehouse": "warehouse", "va
           "data_driven": "data_driven"}
 
 
+GEMM_PRECISIONS = ("fp32", "bf16")
+
+
+def check_gemm_precision(value):
+    """`gemm_precision` of the fused engine / Trainer: "fp32" (the default, the 1e-5 parity contract) or "bf16" (opt-in
+    bf16 matrix-core GEMMs for the wide hidden-to-hidden layers, outside that contract).  Anything else raises ValueError."""
+    if not isinstance(value, str) or value not in GEMM_PRECISIONS:
+        raise ValueError(f"gemm_precision must be one of {GEMM_PRECISIONS}, got {value!r}")
+    return value
+
+
 def _pad32(n):
     return (n + 31) // 32 * 32
 
@@ -160,6 +171,12 @@ class FusedRollout:
         # scenarios) and loses at the full batch (231 vs 180 ms) - its H x H layers run at the tiled GEMM's rate (36-40 us per 8,192
         # columns) while the head / env / first-layer stages of a block serialise behind them on one wavefront per SIMD
         self.use_wide = False
+        # "bf16": the hidden-to-hidden layers (0 < i < L-1, input = an ELU activation, N and K multiples of 32 and >= 128) run their
+        # forward, input gradient and weight gradient on the bf16 matrix cores (csrc/linear_bf16.hip: operands rounded to bf16,
+        # FP32 accumulation, bias and ELU); every other layer, the fused tail, heads and env step stay FP32.  OUTSIDE the 1e-5 parity
+        # contract of the default "fp32".  `bf16_layers`: the layer indices that ran in bf16 in the last run.
+        self.gemm_precision = "fp32"
+        self.bf16_layers = []
         # data_driven on small batches (what the reference trains it on: 72 products): all periods in ONE forward and ONE backward
         # launch (csrc/horizon_rollout.hip).  Measured against the per-period kernels on the real-data shape (tools/
         # horizon_crossover.py, profiles/r04_horizon_crossover.json): 2.3 vs 8.7 ms (replayed) at 72 scenarios, 3.4 vs 10.2 at 4,096,
@@ -234,7 +251,7 @@ class FusedRollout:
         key = (prob.B, T, bool(train), prob.S, prob.Wn, prob.E, prob.Ws, prob.Ww, prob.We, self.batch_wgrad, self.use_thin,
                self.eval_history, self.small_wgrad_in_kernel, extra_rows, self.small_lane_scenarios, self.use_horizon,
                self.horizon_max_scenarios, getattr(self, "_shift_hint", 0), self.fuse_tail, self.tail_max_scenarios,
-               self.tail_bwd_min_scenarios, self.fuse_head_env, self.use_wide)
+               self.tail_bwd_min_scenarios, self.fuse_head_env, self.use_wide, check_gemm_precision(self.gemm_precision))
         if self._key == key:
             return
         dev, ld = self.device, prob.ldb
@@ -378,6 +395,15 @@ class FusedRollout:
         # engine copies of the weights: rows padded to a multiple of 32 floats so every A-tile load is a float4
         self.Wp = [z(gd[i + 1], _pad32(gd[i])) for i in range(L)]
         self.Wt = [z(gd[i] + (1 if i == 0 else 0), _pad32(gd[i + 1])) for i in range(L)]   # (layer 0: + the bias row, see above)
+        # gemm_precision "bf16": bf16 copies of W ([N][K]) and W^T ([K][N]) of the eligible hidden layers, refreshed in place every
+        # run next to Wp / Wt (so a captured graph reads the optimizer's latest weights)
+        bf16 = self.gemm_precision == "bf16"
+        if bf16 and self.use_wide:
+            raise ValueError("gemm_precision='bf16' is not available on the whole-horizon wide route (use_wide)")
+        self._bf16 = [i for i in range(1, L - 1) if bf16 and ops.linear_bf16_ok(gd[i + 1], gd[i])]
+        bz = lambda *shape: torch.zeros(*shape, dtype=torch.bfloat16, device=dev)  # noqa: E731
+        self.Wb = {i: bz(gd[i + 1], _pad32(gd[i])) for i in self._bf16}
+        self.Wtb = {i: bz(gd[i], _pad32(gd[i + 1])) for i in self._bf16}
         # whole-horizon forward of the wide policy: every hidden layer 512 wide, history kept, shapes in the kernel's range
         if self.use_wide and not _lib.has_experiments():
             raise ValueError("use_wide: the whole-horizon kernels of the wide policy are an experiment outside the default library "
@@ -528,6 +554,8 @@ class FusedRollout:
         if demand_soa.shape[0] < T + shift:
             raise ValueError("Current period is greater than the number of periods in the data")
 
+        if self.small is not None or self.horizon is not None:
+            self.bf16_layers = []   # (the whole-horizon routes' policies have no eligible layers: they run as before)
         if self.small is not None:
             return self._run_small(data, prob, T, B, ld, shift, demand_soa, ignore_periods, train, grad_scale,
                                    accumulate_grads, assign_grads)
@@ -551,6 +579,10 @@ class FusedRollout:
             w = m.weight.detach() if (rows is None or i < L - 1) else m.weight.detach()[rows]
             self.Wp[i][:, :self.gd[i]].copy_(w)
             self.Wt[i][:self.gd[i], :self.gd[i + 1]].copy_(w.t())
+            if i in self.Wb:   # (torch's float -> bfloat16 cast: round to nearest even)
+                self.Wb[i][:, :self.gd[i]].copy_(w)
+                self.Wtb[i][:self.gd[i], :self.gd[i + 1]].copy_(w.t())
+        self.bf16_layers = list(self._bf16)
         biases = [m.bias.detach() if m.bias is not None else None for m in lins]
         if biases[0] is not None:
             self.Wt[0][self.gd[0], :self.gd[1]].copy_(biases[0])
@@ -863,6 +895,36 @@ class FusedRollout:
             self._graphs[name] = g
         g.replay()
 
+    # ---- the GEMMs of one layer: FP32 (linear_mfma.hip), or bf16 (linear_bf16.hip) for the layers in bf16_layers -------------
+    # (layer i > 0 of the per-period routes; its input is the previous layer's ELU output)
+    def _linear_fwd(self, i, x, y):
+        B, biases, n, k = self._ctx[2], self._ctx[8], self.gd[i + 1], self.gd[i]
+        if i in self.Wb:
+            self._k(f"fwd_bf16_{n}x{k}", ops.linear_bf16_fwd, self.Wb[i][:, :k], biases[i], x, y, B, _lib.NIC_ACT_ELU)
+        else:
+            self._k(f"fwd_{n}x{k}", ops.linear_fwd, self._ctx[6][i], biases[i], x, y, B, _lib.NIC_ACT_ELU)
+
+    def _linear_dgrad(self, i, d, x_in, dx):
+        B, n, k = self._ctx[2], self.gd[i + 1], self.gd[i]
+        if i in self.Wtb:
+            self._k(f"dgrad_bf16_{n}x{k}", ops.linear_bf16_dgrad, self.Wtb[i][:k, :n], d, x_in, dx, B, _lib.NIC_ACT_ELU, False)
+        else:
+            self._k(f"dgrad_{n}x{k}", ops.linear_dgrad, self._ctx[7][i], d, x_in, dx, B, _lib.NIC_ACT_ELU, False)
+
+    def _linear_wgrad(self, i, d, x_in):
+        B, n, k = self._ctx[2], self.gd[i + 1], self.gd[i]
+        if i in self.Wb:
+            self._k(f"wgrad_bf16_{n}x{k}", ops.linear_bf16_wgrad, d, x_in, self.slabs[i], B)
+        else:
+            self._k(f"wgrad_{n}x{k}", ops.linear_wgrad, d, x_in, self.slabs[i], B)
+
+    def _linear_wgrad_periods(self, i, dz_hist, x_hist):
+        B, n, k = self._ctx[2], self.gd[i + 1], self.gd[i]
+        if i in self.Wb:
+            self._k(f"wgradT_bf16_{n}x{k}", ops.linear_bf16_wgrad_periods, dz_hist, x_hist, self.slabs[i], B)
+        else:
+            self._k(f"wgradT_{n}x{k}", ops.linear_wgrad_periods, dz_hist, x_hist, self.slabs[i], B)
+
     def _launch_forward(self):
         prob, T, B, ld, shift, train, Wv, Wtv, biases, L, demand_soa = self._ctx
         ub = self._ub_now
@@ -889,7 +951,7 @@ class FusedRollout:
                 elif i == 0 and self._thin_in:   # short contraction, many rows: the write-bound streamed forward (thin_layer.hip)
                     self._k(f"fwd_{self.gd[1]}x{self.gd[0]}", ops.linear_fwd_thin_in, Wtv[0], biases[0], x, y, B, _lib.NIC_ACT_ELU)
                 else:
-                    self._k(f"fwd_{self.gd[i + 1]}x{self.gd[i]}", ops.linear_fwd, Wv[i], biases[i], x, y, B, _lib.NIC_ACT_ELU)
+                    self._linear_fwd(i, x, y)
                 x = y
             Z = self.logits[row]
             rows_kw = {}
@@ -993,7 +1055,7 @@ class FusedRollout:
             x = self.hidden[0][hs]
             for i in range(1, L - 1):
                 y = self.hidden[i][hs]
-                self._k(f"fwd_{self.gd[i + 1]}x{self.gd[i]}", ops.linear_fwd, Wv[i], biases[i], x, y, B, _lib.NIC_ACT_ELU)
+                self._linear_fwd(i, x, y)
                 x = y
             desc = self._tail_desc(t, self.states[cur], self.orders[row])
             self._k("tail_fwd", ops.period_tail_fwd, desc, x, self.logits[row], self.states[nxt], self.rewards[t],
@@ -1017,17 +1079,17 @@ class FusedRollout:
             for i in range(L - 2, -1, -1):
                 x_in = self.hidden[i - 1][t] if i > 0 else self.states[t][:self.F]
                 if hist is None:
-                    self._k(f"wgrad_{self.gd[i + 1]}x{self.gd[i]}", ops.linear_wgrad, d, x_in, self.slabs[i], B)
+                    self._linear_wgrad(i, d, x_in)
                 if i > 0:
                     dxi = hist[i - 1][t] if hist is not None else self.dH[i & 1][:self.gd[i]]
-                    self._k(f"dgrad_{self.gd[i + 1]}x{self.gd[i]}", ops.linear_dgrad, Wtv[i], d, x_in, dxi, B, _lib.NIC_ACT_ELU, False)
+                    self._linear_dgrad(i, d, x_in, dxi)
                     d = dxi
                 # (i == 0: the first layer's input gradient is the first stage of the NEXT tail launch; period 0's is not needed)
             g_next, g_cur = g_cur, g_next
         if hist is not None:
             for i in range(L - 1):
                 x_hist = self.hidden[i - 1] if i > 0 else self.states[:T, :self.F]
-                self._k(f"wgradT_{self.gd[i + 1]}x{self.gd[i]}", ops.linear_wgrad_periods, hist[i], x_hist, self.slabs[i], B)
+                self._linear_wgrad_periods(i, hist[i], x_hist)
         for i in range(L):
             ops.wgrad_reduce(self.slabs[i], self.gw[i], self.gb[i], self.gd[i], 1.0)
 
@@ -1090,10 +1152,9 @@ class FusedRollout:
                     d = dx
                     continue
                 if hist is None or (i == L - 1 and last_hist is None):  # (else: contracted over all periods after the sweep)
-                    self._k(f"wgrad_{self.gd[i + 1]}x{self.gd[i]}", ops.linear_wgrad, d, x_in, self.slabs[i], B)
+                    self._linear_wgrad(i, d, x_in)
                 if i > 0:
-                    self._k(f"dgrad_{self.gd[i + 1]}x{self.gd[i]}", ops.linear_dgrad, Wtv[i], d, x_in, dx, B,
-                            _lib.NIC_ACT_ELU, False)
+                    self._linear_dgrad(i, d, x_in, dx)
                     d = dx
                 elif not detached_input:   # (only the state rows of the input carry a gradient back in time)
                     self._k(f"dgrad_{self.gd[1]}x{self.gd[0]}", ops.linear_dgrad, Wtv[0][:self.F_dyn], d, None,
@@ -1106,8 +1167,7 @@ class FusedRollout:
                     continue  # its weight gradient was accumulated period by period (fused thin-layer backward / no history)
                 x_hist = self.hidden[i - 1] if i > 0 else self.states[:T, :self.F]
                 dz_hist = self.dZhist[i] if i < L - 1 else self.dZlast_hist
-                self._k(f"wgradT_{self.gd[i + 1]}x{self.gd[i]}", ops.linear_wgrad_periods, dz_hist, x_hist,
-                        self.slabs[i], B)
+                self._linear_wgrad_periods(i, dz_hist, x_hist)
         for i in range(L):
             if i == L - 1 and self.live_rows is not None:   # compact logits layer: reduce, then scatter into the parameter's rows
                 ops.wgrad_reduce(self.slabs[i], self.gw_c, self.gb_c, self.gd[i], 1.0)

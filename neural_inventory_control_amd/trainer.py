@@ -93,6 +93,9 @@ class Trainer:
         # engine measures host enqueue time against GPU time on a shape's second training step and replays only if the step is
         # launch-bound; `trainer_params.use_rollout_graph` in main_run)
         self.use_rollout_graph = "auto"
+        # MLP engine's GEMMs: "fp32" (default; the 1e-5 parity contract) or "bf16" (opt-in bf16 matrix cores for the wide hidden
+        # layers, outside that contract: FusedRollout.gemm_precision; `trainer_params.gemm_precision` in main_run)
+        self.gemm_precision = "fp32"
         # captured steps copy every batch tensor into the graph's static buffers before a replay; True = skip tensors presented
         # again unchanged (same object, address and version counter) - for callers that never rewrite a batch tensor in place
         # through a raw pointer (bench.py: one resident batch)
@@ -129,24 +132,27 @@ class Trainer:
         key = dev.index if dev.index is not None else torch.cuda.current_device()
         if key not in cls._hazard_guard:
             ok = False
-            try:
-                p_ = torch.nn.Parameter(torch.ones(4, device=dev))
-                keep = (p_ * 2.0).sum()   # noqa: F841  (holds the graph, and with it the accumulator bound to the default stream)
-                side = torch.cuda.Stream(device=dev)
-                side.wait_stream(torch.cuda.current_stream(dev))
-                was = torch.is_warn_always_enabled()
-                torch.set_warn_always(True)
+            # (under grad mode whatever the caller's: the first call may come from an evaluation epoch under no_grad, where the probe
+            # would build no autograd graph, fail, and leave "auto" without step captures for the rest of the process)
+            with torch.enable_grad():
                 try:
-                    with warnings.catch_warnings(record=True) as caught:
-                        warnings.simplefilter("always")
-                        with torch.cuda.stream(side):
-                            torch.autograd.grad((p_ * 3.0).sum(), [p_])
-                finally:
-                    torch.set_warn_always(was)
-                torch.cuda.current_stream(dev).wait_stream(side)
-                ok = bool(cls._autograd_stream_warnings(caught))
-            except Exception:
-                ok = False
+                    p_ = torch.nn.Parameter(torch.ones(4, device=dev))
+                    keep = (p_ * 2.0).sum()   # noqa: F841  (holds the graph, and with it the accumulator bound to the default stream)
+                    side = torch.cuda.Stream(device=dev)
+                    side.wait_stream(torch.cuda.current_stream(dev))
+                    was = torch.is_warn_always_enabled()
+                    torch.set_warn_always(True)
+                    try:
+                        with warnings.catch_warnings(record=True) as caught:
+                            warnings.simplefilter("always")
+                            with torch.cuda.stream(side):
+                                torch.autograd.grad((p_ * 3.0).sum(), [p_])
+                    finally:
+                        torch.set_warn_always(was)
+                    torch.cuda.current_stream(dev).wait_stream(side)
+                    ok = bool(cls._autograd_stream_warnings(caught))
+                except Exception:
+                    ok = False
             cls._hazard_guard[key] = ok
         return cls._hazard_guard[key]
 
@@ -360,7 +366,7 @@ class Trainer:
             eng.use_graph = self.use_rollout_graph   # (both engines: True / False / "auto" = by measurement per shape)
             if hasattr(eng, "zero_lead_orders"):   # (the Simulator's rule for orders without a lead time also holds on the fused route)
                 eng.zero_lead_orders = getattr(simulator, "zero_lead_orders", "drop")
-            for opt_ in ("fuse_tail", "use_wide", "use_period_kernel", "use_period_bwd"):   # (A/B switches of the engines' routes: set on the trainer, handed on)
+            for opt_ in ("fuse_tail", "use_wide", "use_period_kernel", "use_period_bwd", "gemm_precision"):   # (A/B switches of the engines' routes: set on the trainer, handed on)
                 if hasattr(self, opt_) and hasattr(eng, opt_):
                     setattr(eng, opt_, getattr(self, opt_))
             if direct and train:
