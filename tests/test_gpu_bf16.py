@@ -10,6 +10,7 @@ from collections import defaultdict
 import pytest
 import torch
 
+import bf16_emulation as emu
 from neural_inventory_control_amd import _lib, main_run, ops, workloads
 from neural_inventory_control_amd.data_handling import Scenario
 from neural_inventory_control_amd.loss_functions import PolicyLoss
@@ -18,26 +19,12 @@ from neural_inventory_control_amd.rollout import FusedRollout
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-U = 2.0 ** -24
-
-
-def _bf(t):
-    return t.to(torch.bfloat16).double()
-
-
-def _elu(z):
-    return torch.where(z > 0, z, torch.expm1(torch.clamp(z, max=0)))
+U = emu.U
+_bf, _elu, _within = emu.bf, emu.elu, emu.within
 
 
 def _rand(*shape, scale=1.0, gen=None):
     return (torch.randn(*shape, generator=gen, device=DEV) * scale).float()
-
-
-def _within(got, ref, tol, what):
-    err = (got.double() - ref).abs()
-    worst = float((err / tol).max())
-    assert worst <= 1.0, f"{what}: worst error / bound = {worst:.3g}"
-    return worst
 
 
 def _operands(N, K, nS, ldb, seed):
@@ -60,12 +47,8 @@ def test_forward_against_exact_emulation(N, K, nS, ldb):
     Y = torch.full((N, ldb), 12345.0, device=DEV)
     ops.linear_bf16_fwd(Wb[:, :K], bias, X, Y, nS, _lib.NIC_ACT_ELU)
     nc = (nS + 3) // 4 * 4
-    a, b = _bf(W), _bf(X[:, :nc])
-    z = a @ b
-    S = a.abs() @ b.abs()
-    zb = z + bias.double()[:, None]
-    tol = K * U * S + 2 * U * zb.abs() + 3e-7 * (1 + zb.abs())   # accumulation + bias add + the ELU's approximation
-    _within(Y[:, :nc], _elu(zb), tol, "forward")
+    ref, tol = emu.forward(W, X[:, :nc], bias)   # accumulation + bias add + the ELU's approximation
+    _within(Y[:, :nc], ref, tol, "forward")
     # padding columns: as the FP32 kernel leaves them
     Yf = torch.full((N, ldb), 12345.0, device=DEV)
     ops.linear_fwd(W, bias, X, Yf, nS, _lib.NIC_ACT_ELU)
@@ -73,7 +56,8 @@ def test_forward_against_exact_emulation(N, K, nS, ldb):
     # identity activation, no bias
     Y2 = torch.empty(N, ldb, device=DEV)
     ops.linear_bf16_fwd(Wb[:, :K], None, X, Y2, nS, _lib.NIC_ACT_NONE)
-    _within(Y2[:, :nc], z, K * U * S + 1e-30, "forward (no bias, identity)")
+    ref, tol = emu.forward(W, X[:, :nc], None, act_elu=False)
+    _within(Y2[:, :nc], ref, tol, "forward (no bias, identity)")
 
 
 @pytest.mark.parametrize("N,K,nS,ldb", SHAPES)
@@ -90,13 +74,7 @@ def test_dgrad_against_exact_emulation(N, K, nS, ldb, accumulate):
     dX = prev.clone()
     ops.linear_bf16_dgrad(Wtb[:, :N], dY, H, dX, nS, _lib.NIC_ACT_ELU, accumulate)
     nc = (nS + 3) // 4 * 4
-    a, b = _bf(W.t()), _bf(dY[:, :nc])
-    z = a @ b
-    S = a.abs() @ b.abs()
-    h = H[:, :nc].double()
-    d = torch.where(h > 0, torch.ones_like(h), h + 1)
-    ref = z * d + (prev[:, :nc].double() if accumulate else 0)
-    tol = (N * U * S + 2 * U * z.abs()) * d + 2 * U * ref.abs() + 1e-30
+    ref, tol = emu.dgrad(W.t(), dY[:, :nc], H[:, :nc], prev[:, :nc] if accumulate else None)
     _within(dX[:, :nc], ref, tol, "dgrad")
     assert torch.equal(dX[:, nc:], prev[:, nc:])   # (the FP32 kernel writes columns < round_up(n, 4) only, too)
 
@@ -112,11 +90,9 @@ def test_wgrad_against_exact_emulation(N, K, nS, ldb):
     ops.linear_bf16_wgrad(dY, X, slab, nS)   # (a second period adds to the slab)
     gw, gb = torch.empty(N, K, device=DEV), torch.empty(N, device=DEV)
     ops.wgrad_reduce(slab, gw, gb, K, 1.0)
-    a, b = _bf(dY[:, :nS]), _bf(X[:, :nS])
-    ref, S = 2 * (a @ b.t()), 2 * (a.abs() @ b.abs().t())
-    _within(gw, ref, 2 * nS * U * S + 1e-30, "wgrad")
-    dyd = dY[:, :nS].double()
-    _within(gb, 2 * dyd.sum(1), 2 * nS * U * 2 * dyd.abs().sum(1) + 1e-30, "bias gradient")
+    ref, tol, ref_b, tol_b = emu.wgrad(dY[:, :nS], X[:, :nS], repeats=2)
+    _within(gw, ref, tol, "wgrad")
+    _within(gb, ref_b, tol_b, "bias gradient")
 
 
 @pytest.mark.parametrize("nS,ldb", [(1024, 1024), (1000, 1152)])
@@ -131,11 +107,9 @@ def test_wgrad_periods_against_exact_emulation(nS, ldb):
     ops.linear_bf16_wgrad_periods(dYh[:, :N], Xh[:, :K], slab, nS)
     gw, gb = torch.empty(N, K, device=DEV), torch.empty(N, device=DEV)
     ops.wgrad_reduce(slab, gw, gb, K, 1.0)
-    a = _bf(dYh[:, :N, :nS]).permute(1, 0, 2).reshape(N, T * nS)
-    b = _bf(Xh[:, :K, :nS]).permute(1, 0, 2).reshape(K, T * nS)
-    _within(gw, a @ b.t(), T * nS * U * (a.abs() @ b.abs().t()) + 1e-30, "wgrad over periods")
-    dyd = dYh[:, :N, :nS].double()
-    _within(gb, dyd.sum((0, 2)), T * nS * U * dyd.abs().sum((0, 2)) + 1e-30, "bias gradient over periods")
+    ref, tol, ref_b, tol_b = emu.wgrad_periods(dYh[:, :N, :nS], Xh[:, :K, :nS])
+    _within(gw, ref, tol, "wgrad over periods")
+    _within(gb, ref_b, tol_b, "bias gradient over periods")
     # determinism: the same launch again gives the same bits
     slab2 = torch.zeros_like(slab)
     ops.linear_bf16_wgrad_periods(dYh[:, :N], Xh[:, :K], slab2, nS)
@@ -157,6 +131,409 @@ def test_kernels_deterministic():
         outs.append((Y, dX, slab))
     for a, b in zip(*outs):
         assert torch.equal(a, b)
+
+
+# ---- the shape sweep: everything nic_linear_bf16_ok admits, not only multiples of 128 ------------------------------------------
+# Every case: NaN-filled outputs (with guard rows behind them), random garbage in every input column at or beyond
+# round_up(n, 4) (the weight gradient: beyond n), zeros in [n, round_up(n, 4)) as the engine keeps them, an ldb well above
+# round_up(n, 4), and weights that are a view into a wider bf16 buffer (row stride K + 40, a multiple of 8, garbage around them).
+# The bounds are tests/bf16_emulation.py's (tests/test_bf16_emulation_host.py shows what they catch); each test prints its worst
+# error / bound and the case it came from.  Measured on MI355X: DESIGN.md section 11.
+
+SWEEP_NK = [(128, 128), (160, 224), (288, 160), (512, 160), (224, 512)]
+SWEEP_N_WX = [1, 3, 4, 5, 33, 63, 64, 65, 1000]
+SWEEP_N_WGRAD = [1, 31, 100, 1001, 4099]
+NAN = float("nan")
+
+
+def _r4(n):
+    return (n + 3) // 4 * 4
+
+
+def _last_kernel():
+    return _lib.lib().nic_last_kernel().decode()
+
+
+def _cu_count():
+    """the library's CU count (nic::cu_count(): the device's multiprocessor count)"""
+    return torch.cuda.get_device_properties(torch.device(DEV)).multi_processor_count
+
+
+def _wide_bf16(W, g):
+    """bf16(W) as a view into a wider buffer: row stride K + 40, first column 8 (16-byte aligned), garbage everywhere else"""
+    rows, cols = W.shape
+    buf = _rand(rows, cols + 40, scale=100.0, gen=g).to(torch.bfloat16)
+    view = buf[:, 8:8 + cols]
+    view.copy_(W)
+    assert view.stride(0) == cols + 40 and view.data_ptr() % 16 == 0
+    return view
+
+
+def _activations(rows, n, ldb, g, scale=None, zero_to=None):
+    """[rows][ldb]: data in columns < n (an ELU activation, or scale * N(0, 1)), zeros up to `zero_to`, garbage behind"""
+    t = _rand(rows, ldb, scale=50.0, gen=g)
+    data = _rand(rows, n, gen=g)
+    t[:, :n] = _elu(data.double()).float() if scale is None else data * scale
+    t[:, n:zero_to if zero_to is not None else n] = 0.0
+    return t
+
+
+def _nan_out(rows, ldb, guard=3):
+    buf = torch.full((rows + guard, ldb), NAN, device=DEV)
+    return buf, buf[:rows]
+
+
+def _all_nan(t):
+    return bool(torch.isnan(t).all())
+
+
+def _forward_case(N, K, n, seed):
+    """one forward launch with bias + ELU and one without: (worst ratio, kernel name)"""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    nc = _r4(n)
+    ldb = nc + 72
+    W = _rand(N, K, scale=K ** -0.5, gen=g)
+    Wv = _wide_bf16(W, g)
+    X = _activations(K, n, ldb, g, zero_to=nc)
+    bias = _rand(N, scale=0.1, gen=g)
+    worst = 0.0
+    for b, act in ((bias, _lib.NIC_ACT_ELU), (None, _lib.NIC_ACT_NONE)):
+        buf, Y = _nan_out(N, ldb)
+        ops.linear_bf16_fwd(Wv, b, X, Y, n, act)
+        kernel = _last_kernel()
+        ref, tol = emu.forward(W, X[:, :nc], b, act_elu=act == _lib.NIC_ACT_ELU)
+        worst = max(worst, _within(Y[:, :nc], ref, tol, f"forward {N}x{K}, n={n}, act={act} ({kernel})"))
+        assert _all_nan(Y[:, nc:]) and _all_nan(buf[N:]), f"forward {N}x{K}, n={n}: wrote beyond round_up(n, 4) or beyond row N"
+    return worst, kernel
+
+
+def _dgrad_case(N, K, n, seed):
+    """dgrad with ELU' and without an activation (Hprev = None), with and without accumulate: (worst ratio, kernel name)"""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    nc = _r4(n)
+    ldb = nc + 72
+    Wt = _rand(K, N, scale=K ** -0.5, gen=g)
+    Wtv = _wide_bf16(Wt, g)
+    dY = _activations(N, n, ldb, g, scale=1e-3, zero_to=nc)
+    H = _activations(K, nc, ldb, g)
+    prev = _rand(K, nc, scale=1e-3, gen=g)
+    worst = 0.0
+    for h, act in ((H, _lib.NIC_ACT_ELU), (None, _lib.NIC_ACT_NONE)):
+        for accumulate in (0, 1):
+            buf, dX = _nan_out(K, ldb)
+            if accumulate:
+                dX[:, :nc] = prev
+            ops.linear_bf16_dgrad(Wtv, dY, h, dX, n, act, accumulate)
+            kernel = _last_kernel()
+            ref, tol = emu.dgrad(Wt, dY[:, :nc], h[:, :nc] if h is not None else None, prev if accumulate else None)
+            what = f"dgrad {N}x{K}, n={n}, act_prev={act}, accumulate={accumulate} ({kernel})"
+            worst = max(worst, _within(dX[:, :nc], ref, tol, what))
+            assert _all_nan(dX[:, nc:]) and _all_nan(buf[K:]), f"{what}: wrote beyond round_up(n, 4) or beyond row K"
+    return worst, kernel
+
+
+@pytest.mark.parametrize("N,K", SWEEP_NK)
+def test_sweep_forward(N, K):
+    worst = max((_forward_case(N, K, n, 100 + n) + (n,) for n in SWEEP_N_WX), key=lambda r: r[0])
+    print(f"RATIO forward {N}x{K}: worst error / bound {worst[0]:.4f} at n={worst[2]} ({worst[1]})")
+
+
+@pytest.mark.parametrize("N,K", SWEEP_NK)
+def test_sweep_dgrad(N, K):
+    worst = max((_dgrad_case(N, K, n, 200 + n) + (n,) for n in SWEEP_N_WX), key=lambda r: r[0])
+    print(f"RATIO dgrad {N}x{K}: worst error / bound {worst[0]:.4f} at n={worst[2]} ({worst[1]})")
+
+
+@pytest.mark.parametrize("N,K", [(160, 224), (288, 160)])
+@pytest.mark.parametrize("entry", ["forward", "dgrad"])
+def test_partial_row_tiles_in_both_tilings(entry, N, K):
+    """Output rows that are no multiple of the tile height, in the 64 x 64 tiling (a small batch) and in the 128 x 128 tiling,
+    which launch_wx takes from two row-tile x column-tile workgroups per CU: the column count is worked out from the CU count."""
+    case, M, epi = (_forward_case, N, 0) if entry == "forward" else (_dgrad_case, K, 1)
+    assert M % 128 != 0 and M % 64 != 0
+    row_tiles = (M + 127) // 128
+    col_tiles = (2 * _cu_count() + row_tiles - 1) // row_tiles
+    n_big = 128 * col_tiles - 61
+    for n, variant in ((1000, f"bf16_wx_kernel<1,1,{epi}>"), (n_big, f"bf16_wx_kernel<2,2,{epi}>")):
+        worst, kernel = case(N, K, n, 300 + n)
+        assert kernel == variant, (kernel, variant, n)
+        print(f"RATIO {entry} {N}x{K}: worst error / bound {worst:.4f} at n={n} ({kernel}, {M} output rows)")
+
+
+def _prefilled_slab(slots, N, lds):
+    """a known pattern without zeros, small next to the sums (so that the bound's term for it stays small): 2^-16 * (1..7)"""
+    i = torch.arange(slots * N * lds, device=DEV)
+    return (((i % 7) + 1).float() * 2.0 ** -16 * (1 - 2 * (i % 2)).float()).view(slots, N, lds)
+
+
+def _check_slab(slab, before, owned, K, ref, tol, ref_b, tol_b, what):
+    """slab - before, summed over the slots, against the emulation; slots outside `owned` and the columns beyond K + 1 bit-identical"""
+    for s in range(slab.shape[0]):
+        if s not in owned:
+            assert torch.equal(slab[s], before[s]), f"{what}: slot {s} is not the launch's, but it changed"
+    assert torch.equal(slab[:, :, K + 1:], before[:, :, K + 1:]), f"{what}: slab columns beyond K + 1 changed"
+    delta = (slab.double() - before.double()).sum(0)
+    return max(_within(delta[:, :K], ref, tol, what), _within(delta[:, K], ref_b, tol_b, what + ", bias column"))
+
+
+@pytest.mark.parametrize("N,K", SWEEP_NK)
+def test_sweep_wgrad(N, K):
+    lds = _r4(K + 1) + 4
+    worst, many = (0.0, None), 0.0
+    for n in SWEEP_N_WGRAD:
+        g = torch.Generator(device=DEV).manual_seed(400 + n)
+        ldb = _r4(n) + 72
+        dY = _activations(N, n, ldb, g, scale=1e-3)   # (garbage from column n on: it must not count)
+        X = _activations(K, n, ldb, g, scale=1.0)
+        for slots in (1, 3, 64):
+            before = _prefilled_slab(slots, N, lds)
+            slab = before.clone()
+            ops.linear_bf16_wgrad(dY, X, slab, n)
+            assert _last_kernel() == "bf16_wgrad_kernel<2,2>"
+            # slots the launch owns (wgrad_bf16 in csrc/linear_bf16.hip): chunks of round_up(ceil(n / slots), 32) scenarios
+            chunk = ((n + slots - 1) // slots + 31) // 32 * 32
+            owned = {s for s in range(slots) if s * chunk < n}
+            ref, tol, ref_b, tol_b = emu.wgrad(dY[:, :n], X[:, :n], base_w=before[:, :, :K].abs().amax(0),
+                                               base_b=before[:, :, K].abs().amax(0))
+            r = _check_slab(slab, before, owned, K, ref, tol, ref_b, tol_b, f"wgrad {N}x{K}, n={n}, {slots} slots")
+            worst = max(worst, (r, f"n={n}, {slots} slots ({len(owned)} owned)"))
+            many = max(many, r if n > 1 else 0.0)
+    # (n = 1 into a pre-filled slab: ONE rounding of base + product, which is what the bound allows - a ratio just below 1)
+    print(f"RATIO wgrad {N}x{K}: worst error / bound {worst[0]:.4f} at {worst[1]}; from 31 scenarios up {many:.4f}")
+
+
+def _period_factors(n_slots, n, T):
+    """`period_factors` and `wgrad_bf16` of csrc/linear_bf16.hip restated: (scenario splits, period groups, chunk, periods per
+    group, flush).  It CHOOSES the cases below and names the slots a launch owns; no numerical result is judged by it."""
+    ss = max(1, min(n_slots, max(1, n // 128)))
+    groups = max(1, min(n_slots // ss, T))
+    chunk = ((n + ss - 1) // ss + 31) // 32 * 32
+    return ss, groups, chunk, (T + groups - 1) // groups, max(1, 8192 // chunk)
+
+
+# (slots, n, T, N, K, what the case is there for, a check of the restated factors that says so)
+PERIOD_CASES = [
+    (2, 4096, 11, 160, 224, "flush segments of 4 + 4 + 3 periods", lambda ss, g, chunk, ppg, flush: (ss, g, chunk, ppg, flush) == (2, 1, 2048, 11, 4)),
+    (4, 4099, 9, 288, 160, "segments of 7 + 2 periods, ragged chunks", lambda ss, g, chunk, ppg, flush: (ss, g, chunk, ppg, flush) == (4, 1, 1056, 9, 7)),
+    (1, 8203, 3, 160, 224, "flush == 1 (chunk >= 8,192): a segment per period", lambda ss, g, chunk, ppg, flush: chunk >= 8192 and flush == 1 and ppg == 3),
+    (6, 300, 7, 160, 224, "3 period groups of 3 + 3 + 1 periods", lambda ss, g, chunk, ppg, flush: (ss, g, ppg) == (2, 3, 3)),
+    (4, 100, 5, 128, 128, "4 groups x 2 periods over T = 5: the last group idle", lambda ss, g, chunk, ppg, flush: (ss, g, ppg) == (1, 4, 2)),
+    (7, 300, 2, 288, 160, "7 slots, 2 x 2 used", lambda ss, g, chunk, ppg, flush: ss * g == 4),
+    (3, 1001, 1, 224, 512, "T = 1", lambda ss, g, chunk, ppg, flush: (ss, g, ppg) == (3, 1, 1)),
+    (64, 100, 13, 512, 160, "64 slots at 100 scenarios: 13 groups of one period", lambda ss, g, chunk, ppg, flush: (ss, g, ppg) == (1, 13, 1)),
+]
+
+
+@pytest.mark.parametrize("slots,n,T,N,K,why,expect", PERIOD_CASES, ids=[c[5] for c in PERIOD_CASES])
+def test_wgrad_periods_slot_splits_and_flush_segments(slots, n, T, N, K, why, expect):
+    ss, groups, chunk, ppg, flush = _period_factors(slots, n, T)
+    assert expect(ss, groups, chunk, ppg, flush), (why, ss, groups, chunk, ppg, flush)
+    g = torch.Generator(device=DEV).manual_seed(500 + n + T)
+    ldb, lds = _r4(n) + 72, _r4(K + 1) + 4
+    # histories whose period strides are not the matrices' sizes; garbage from column n on
+    dYh = torch.stack([_activations(N + 5, n, ldb, g, scale=1e-3) for _ in range(T)])
+    Xh = torch.stack([_activations(K + 3, n, ldb, g, scale=1.0) for _ in range(T)])
+    owned = {grp * ss + s for grp in range(groups) for s in range(ss) if s * chunk < n and grp * ppg < T}
+    before = _prefilled_slab(slots, N, lds)
+    slabs = []
+    for _ in range(2):   # twice into fresh slabs: the same bits
+        slab = before.clone()
+        ops.linear_bf16_wgrad_periods(dYh[:, :N], Xh[:, :K], slab, n)
+        slabs.append(slab)
+    assert torch.equal(slabs[0], slabs[1])
+    ref, tol, ref_b, tol_b = emu.wgrad_periods(dYh[:, :N, :n], Xh[:, :K, :n], base_w=before[:, :, :K].abs().amax(0),
+                                               base_b=before[:, :, K].abs().amax(0))
+    r = _check_slab(slabs[0], before, owned, K, ref, tol, ref_b, tol_b, f"wgrad over periods ({why})")
+    # the tile scan (tests/bf16_emulation.py): with T * n terms the dense bound above no longer shows ONE lost or doubled
+    # 32-scenario tile, so the same launch runs m more times on |dY| with every m-th (period, tile) kept - each tile once
+    m = emu.tile_scan_stride(T * n)
+    r_scan = 0.0
+    if m > 1:
+        dYa, Xa = dYh.abs(), Xh.abs()
+        for rr in range(m):
+            mask = emu.tile_mask(T, n, ldb, m, rr, DEV)[:, None, :]
+            dYm = torch.where(mask, dYa, torch.zeros_like(dYa))
+            dYm[:, :, n:] = dYh[:, :, n:]   # (the garbage behind column n stays)
+            slab = torch.zeros(slots, N, lds, device=DEV)
+            ops.linear_bf16_wgrad_periods(dYm[:, :N], Xa[:, :K], slab, n)
+            ref, tol, ref_b, tol_b = emu.wgrad_periods(dYm[:, :N, :n], Xa[:, :K, :n])
+            what = f"wgrad over periods ({why}), tile scan pass {rr} of {m}"
+            r_scan = max(r_scan, _check_slab(slab, torch.zeros_like(slab), owned, K, ref, tol, ref_b, tol_b, what))
+    segments = [min(flush, ppg - p) for p in range(0, ppg, flush)]
+    print(f"RATIO wgrad_periods {N}x{K}: worst error / bound {r:.4f} (tile scan, {m} passes: {r_scan:.4f}) at {slots} slots, "
+          f"n={n}, T={T}: {why}; {ss} scenario splits x {groups} period groups, chunk {chunk}, flush segments of {segments} "
+          f"periods, {len(owned)} slots owned")
+
+
+# ---- special values ------------------------------------------------------------------------------------------------------------
+FLT_MAX = 3.4028234663852886e38   # rounds to +Inf in bf16
+DENORM = 2.0 ** -127              # an FP32 denormal that is a bf16 denormal as well (so are its small multiples)
+
+
+def _special_check(got, ref, tol, clean_rows, clean_cols, what):
+    """NaN and +-Inf exactly where the emulation has them, the bound everywhere else; the clean rows x columns all finite"""
+    got = got.double().cpu()
+    assert torch.equal(torch.isnan(got), torch.isnan(ref)), f"{what}: NaN pattern differs from the emulation's"
+    inf = torch.isinf(ref)
+    assert torch.equal(torch.isinf(got), inf) and torch.equal(got[inf], ref[inf]), f"{what}: +-Inf pattern differs"
+    fin = torch.isfinite(ref)
+    assert bool(torch.isfinite(got[clean_rows][:, clean_cols]).all()), f"{what}: a special value reached a clean row / column"
+    assert int(fin.sum()) >= len(clean_rows) * len(clean_cols)
+    return _within(got[fin], ref[fin], tol[fin], what)
+
+
+def test_special_values_forward():
+    """+-Inf, NaN, the largest finite float, FP32 denormals and -0.0 in a few scenario columns of X (converted on the device) and
+    a few weight rows (converted by torch): each must stay in its column / row, as in the emulation (evaluated on the CPU).
+    Column 150 of X holds ONLY denormals and weight row 70 is scaled by 2^100: output (70, 150) is an exact sum of products near
+    2^-24 - a conversion (or an MFMA operand path) that flushes denormals gives 0 there, far outside the bound.  No bias and no
+    activation, so that nothing hides them."""
+    N, K, n = 160, 224, 200
+    g = torch.Generator(device=DEV).manual_seed(600)
+    ldb = _r4(n) + 72
+    W = _rand(N, K, scale=K ** -0.5, gen=g)
+    X = _activations(K, n, ldb, g, zero_to=_r4(n))
+    inf = float("inf")
+    for (k, b), v in {(3, 5): inf, (10, 17): -inf, (0, 40): NAN, (100, 77): FLT_MAX, (3, 99): inf, (4, 99): -inf, (7, 130): 1e-40,
+                      (8, 130): -0.0, (9, 131): -FLT_MAX}.items():
+        X[k, b] = v
+    X[:, 150] = DENORM * (1 + torch.arange(K, device=DEV) % 3).float() * (1 - 2 * (torch.arange(K, device=DEV) % 2)).float()
+    x_cols = {5, 17, 40, 77, 99, 130, 131}
+    for (r, k), v in {(20, 50): inf, (33, 1): NAN, (47, 60): FLT_MAX, (60, 20): -0.0, (60, 21): 1e-40, (61, 22): -inf}.items():
+        W[r, k] = v
+    w_rows = {20, 33, 47, 61}
+    W[70] *= 2.0 ** 100   # (row 70: denormal x 2^100 - sums near 2^-24, far above the bound's 1e-30 floor, exact products)
+    Wv = _wide_bf16(W, g)
+    buf, Y = _nan_out(N, ldb)
+    ops.linear_bf16_fwd(Wv, None, X, Y, n, _lib.NIC_ACT_NONE)
+    ref, tol = emu.forward(W.cpu(), X[:, :n].cpu(), None, act_elu=False)
+    clean_rows = [r for r in range(N) if r not in w_rows]
+    clean_cols = [b for b in range(n) if b not in x_cols]
+    r = _special_check(Y[:, :n], ref, tol, clean_rows, clean_cols, "forward with special values")
+    assert 150 in clean_cols and 70 in clean_rows and 1e-12 < abs(float(ref[70, 150])) and float(tol[70, 150]) < 1e-3 * abs(float(ref[70, 150]))
+    assert _all_nan(Y[:, _r4(n):]) and _all_nan(buf[N:])
+    print(f"RATIO forward special values: worst error / bound over the finite outputs {r:.4f}")
+
+
+def test_special_values_wgrad():
+    """The same values in dY and X of the weight gradient (both converted on the device), 3 slots over 200 scenarios: a special
+    value in scenario b of row n of dY reaches row n of the slab (and its bias column) only, one in row k of X column k only.
+    Row 55 of X holds only denormals (judged at row 70 of dY, scaled by 2^110).  The bias column is an FP32 sum of the unrounded dY: the largest finite float stays finite."""
+    N, K, n, slots = 160, 224, 200, 3
+    g = torch.Generator(device=DEV).manual_seed(601)
+    ldb, lds = _r4(n) + 72, _r4(K + 1) + 4
+    dY = _activations(N, n, ldb, g, scale=1e-3)
+    X = _activations(K, n, ldb, g, scale=1.0)
+    inf = float("inf")
+    for (r, b), v in {(5, 10): inf, (12, 100): NAN, (20, 50): FLT_MAX, (25, 60): 1e-40, (26, 61): -0.0, (30, 199): -inf}.items():
+        dY[r, b] = v
+    for (k, b), v in {(30, 150): -inf, (40, 195): FLT_MAX, (50, 61): -0.0, (51, 62): 1e-40, (60, 3): NAN}.items():
+        X[k, b] = v
+    X[55, :n] = DENORM * (1 + torch.arange(n, device=DEV) % 3).float() * (1 - 2 * (torch.arange(n, device=DEV) % 2)).float()
+    dy_rows, x_rows = {5, 12, 20, 30}, {30, 40, 60}
+    dY[70, :n] *= 2.0 ** 110   # (row 70 x the denormal row 55: a sum near 2^-24, far above the bound's 1e-30 floor)
+    slab = torch.zeros(slots, N, lds, device=DEV)
+    ops.linear_bf16_wgrad(dY, X, slab, n)
+    ref, tol, ref_b, tol_b = emu.wgrad(dY[:, :n].cpu(), X[:, :n].cpu())
+    got = slab.double().sum(0).cpu()
+    clean_rows = [r for r in range(N) if r not in dy_rows]
+    clean_cols = [k for k in range(K) if k not in x_rows]
+    r = _special_check(got[:, :K], ref, tol, clean_rows, clean_cols, "wgrad with special values")
+    assert 1e-12 < abs(float(ref[70, 55])) and float(tol[70, 55]) < 1e-3 * abs(float(ref[70, 55]))
+    rb = _special_check(got[:, K:K + 1], ref_b[:, None], tol_b[:, None], clean_rows, [0], "bias gradient with special values")
+    assert bool(torch.isfinite(got[20, K])) and bool((got[:, K + 1:] == 0).all())
+    print(f"RATIO wgrad special values: worst error / bound over the finite outputs {max(r, rb):.4f}")
+
+
+# ---- argument refusal: an error through _lib.check, no launch, the output as it was ----------------------------------------------
+
+def _refused(call, out, message):
+    """`call` must raise NicError naming `message`, launch nothing (the last launched kernel stays the marker launch made here)
+    and leave `out` bit-identical"""
+    marker = torch.zeros(8, 8, device=DEV)
+    ops.round_orders(marker, 8)
+    launched = _last_kernel()
+    assert "bf16" not in launched
+    before = out.clone()
+    with pytest.raises(_lib.NicError, match=message):
+        call()
+    torch.cuda.synchronize()
+    assert _last_kernel() == launched, "a refused call launched a kernel"
+    assert torch.equal(out.view(torch.int32), before.view(torch.int32)), "a refused call changed its output"
+
+
+def _off_by_4_bytes(rows, ldb, fill=0.0):
+    """a [rows][ldb] FP32 view that starts 4 bytes behind a 16-byte boundary"""
+    buf = torch.full((rows * ldb + 4,), fill, device=DEV)
+    view = buf[1:1 + rows * ldb].view(rows, ldb)
+    assert view.data_ptr() % 16 == 4
+    return view
+
+
+def test_bf16_entry_points_refuse_bad_arguments():
+    n, ldb = 100, 128
+    bz = lambda r, c, ld=None: torch.zeros(r, ld or c, dtype=torch.bfloat16, device=DEV)[:, :c]   # noqa: E731
+    fz = lambda r, c=ldb: torch.ones(r, c, device=DEV)   # noqa: E731
+    out = lambda r, c=ldb: torch.full((r, c), NAN, device=DEV)   # noqa: E731
+    ELU, NONE = _lib.NIC_ACT_ELU, _lib.NIC_ACT_NONE
+    shape = "multiples of 32"
+    # -- forward: Y[N][ldb] = W[N][K] X[K][ldb]
+    fwd = lambda W, X, Y, nn=n: (lambda: ops.linear_bf16_fwd(W, None, X, Y, nn, ELU))   # noqa: E731
+    Y = out(128)
+    for N, K in ((96, 128), (128, 130), (144, 128)):
+        Yn = out(N)
+        _refused(fwd(bz(N, K, K + 6 if K % 8 else None), fz(K), Yn), Yn, shape)
+    _refused(fwd(bz(128, 128, 132), fz(128), Y), Y, "multiple of 8")
+    _refused(fwd(bz(128, 128), _off_by_4_bytes(128, ldb, 1.0), Y), Y, "16-byte aligned")
+    Yo = _off_by_4_bytes(128, ldb, NAN)
+    _refused(fwd(bz(128, 128), fz(128), Yo), Yo, "16-byte aligned")
+    Y64 = out(128, 64)
+    _refused(fwd(bz(128, 128), fz(128, 64), Y64), Y64, "n_scenarios")   # ldb = 64 < n = 100
+    _refused(fwd(bz(128, 128), fz(128), Y, 0), Y, "n_scenarios")
+    Y130 = out(128, 130)
+    _refused(fwd(bz(128, 128), fz(128, 130), Y130), Y130, "multiple of 4")
+    with pytest.raises(TypeError):
+        ops.linear_bf16_fwd(torch.zeros(128, 128, device=DEV), None, fz(128), Y, n, ELU)
+    # -- dgrad: dX[K][ldb] = Wt[K][N] dY[N][ldb]
+    dgr = lambda Wt, dY, dX, nn=n: (lambda: ops.linear_bf16_dgrad(Wt, dY, None, dX, nn, NONE, 0))   # noqa: E731
+    dX = out(128)
+    for N, K in ((96, 128), (128, 130), (144, 128)):
+        dXk = out(K)
+        _refused(dgr(bz(K, N), fz(N), dXk), dXk, shape)
+    _refused(dgr(bz(128, 128, 132), fz(128), dX), dX, "multiple of 8")
+    _refused(dgr(bz(128, 128), _off_by_4_bytes(128, ldb, 1.0), dX), dX, "16-byte aligned")
+    dXo = _off_by_4_bytes(128, ldb, NAN)
+    _refused(dgr(bz(128, 128), fz(128), dXo), dXo, "16-byte aligned")
+    dX64 = out(128, 64)
+    _refused(dgr(bz(128, 128), fz(128, 64), dX64), dX64, "n_scenarios")
+    _refused(dgr(bz(128, 128), fz(128), dX, 0), dX, "n_scenarios")
+    dX130 = out(128, 130)
+    _refused(dgr(bz(128, 128), fz(128, 130), dX130), dX130, "multiple of 4")
+    with pytest.raises(TypeError):
+        ops.linear_bf16_dgrad(torch.zeros(128, 128, device=DEV), fz(128), None, dX, n, NONE, 0)
+    # -- weight gradients: slab[slots][N][lds] += dY[N][ldb] X[K][ldb]^T
+    slab = lambda N, K: torch.full((2, N, K + 4), NAN, device=DEV)   # noqa: E731
+    for name, wg in (("single period", lambda dY, X, s, nn=n: (lambda: ops.linear_bf16_wgrad(dY, X, s, nn))),
+                     ("over periods", lambda dY, X, s, nn=n: (lambda: ops.linear_bf16_wgrad_periods(dY[None], X[None], s, nn)))):
+        for N, K in ((96, 128), (128, 130), (144, 128)):
+            s = slab(N, K)
+            _refused(wg(fz(N), fz(K), s), s, shape)
+        s = slab(128, 128)
+        _refused(wg(_off_by_4_bytes(128, ldb, 1.0), fz(128), s), s, "16-byte aligned")
+        _refused(wg(fz(128), _off_by_4_bytes(128, ldb, 1.0), s), s, "16-byte aligned")
+        _refused(wg(fz(128, 64), fz(128, 64), s), s, "n_scenarios")
+        _refused(wg(fz(128), fz(128), s, 0), s, "n_scenarios")
+        _refused(wg(fz(128, 130), fz(128, 130), s), s, "multiple of 4")
+    # -- over periods: no periods; a period stride that is no multiple of 4 elements
+    s = slab(128, 128)
+    hist = torch.ones(3 * (128 * ldb + 2), device=DEV)
+    odd = hist.as_strided((3, 128, ldb), (128 * ldb + 2, ldb, 1))
+    even = torch.ones(3, 128, ldb, device=DEV)
+    _refused(lambda: ops.linear_bf16_wgrad_periods(odd, even, s, n), s, "period strides")
+    _refused(lambda: ops.linear_bf16_wgrad_periods(even, odd, s, n), s, "period strides")
+    lib, st = _lib.lib(), _lib.current_stream()
+    _refused(lambda: _lib.check(lib.nic_linear_bf16_wgrad_periods(even.data_ptr(), even.data_ptr(), s.data_ptr(), s.stride(1), 128, 128,
+                                                                  n, ldb, 2, 0, 128 * ldb, 128 * ldb, st)), s, "n_periods")
 
 
 # ---- the engine ------------------------------------------------------------------------------------------------------------------
@@ -331,3 +708,68 @@ def test_bf16_training_still_learns():
     print(f"dev loss: untrained {untrained}, fp32 {final['fp32']}, bf16 {final['bf16']}")
     assert final["fp32"] < untrained and final["bf16"] < untrained
     assert final["bf16"] <= 1.02 * final["fp32"]
+
+
+# ---- the engine's bf16 layers, checked in place -----------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("graph", [False, True], ids=["eager", "graph"])
+def test_engine_bf16_layers_in_place(graph):
+    """cfg3's setting with hidden layers [256, 160, 288, 96] at 1,037 scenarios x T = 6 in bf16 mode: layers 1 (160 x 256) and
+    2 (288 x 160) are eligible, layer 3 (96 x 288), the first and the logits layer are not.  Three training runs with an Adam step
+    after the first two (with use_graph the third is a replay), then every bf16 launch of the LAST run is judged where it stands:
+    the engine keeps each period's activations (hidden) and pre-activation gradients (dZhist), so each layer's output is compared
+    with the exact emulation of the FP32 input the kernel saw - the bounds of tests/bf16_emulation.py, no recurrence in between.
+    A stale Wb / Wtb copy, a wrong transpose or a history off by one period misses them by orders of magnitude."""
+    n, T = 1037, 6
+    setting, policy, _, _, _ = workloads.get("cfg3")
+    policy = copy.deepcopy(policy)
+    policy["neurons_per_hidden_layer"]["master"] = [256, 160, 288, 96]
+    obs = defaultdict(lambda: None, setting["observation_params"])
+    sc = Scenario(T, setting["problem_params"], setting["store_params"], setting["warehouse_params"], setting["echelon_params"], n,
+                  obs, setting["seeds"], sampler="hip", device=DEV)
+    data = {k: v.to(DEV) for k, v in sc.get_data().items()}
+    torch.manual_seed(13)
+    model = NeuralNetworkCreator().create_neural_network(sc, policy, device=DEV)
+    eng = _engine(model, setting, data, obs, "bf16", use_graph=graph)
+    opt = torch.optim.Adam(model.parameters(), lr=1e-3)
+    for step in range(3):
+        opt.zero_grad()
+        eng.run(data, T, 0, train=True, observation_params=obs)
+        torch.cuda.synchronize()
+        if step < 2:
+            opt.step()   # (the weights move: the next run must refresh its bf16 copies)
+    if graph:
+        assert set(eng._graphs) == {"fwd", "bwd"}
+    lins = model.master_linears()
+    assert [(m.out_features, m.in_features) for m in lins[1:4]] == [(160, 256), (288, 160), (96, 288)]
+    assert eng.bf16_layers == [1, 2]
+    assert eng.dZhist is not None and all(h.shape[0] == T for h in eng.hidden), \
+        "the engine did not keep the per-period histories (period-by-period weight gradients): nothing to check in place"
+    nc = (n + 3) // 4 * 4
+    grads = {id(p): g for p, g in eng.param_grads()}
+    worst = defaultdict(float)
+    for i in eng.bf16_layers:
+        W, bias = lins[i].weight.detach(), lins[i].bias.detach()
+        N, K = W.shape
+        # the copies the kernels read: the bf16 rounding of the weights as the optimizer left them
+        assert torch.equal(eng.Wb[i][:, :K], W.to(torch.bfloat16)), f"layer {i}: stale or wrong Wb"
+        assert torch.equal(eng.Wtb[i][:, :N], W.t().to(torch.bfloat16)), f"layer {i}: stale or wrong Wtb"
+        for t in range(T):
+            x, y = eng.hidden[i - 1][t], eng.hidden[i][t]
+            ref, tol = emu.forward(W, x[:, :nc], bias)
+            worst["forward"] = max(worst["forward"], _within(y[:, :nc], ref, tol, f"layer {i}, period {t}: forward"))
+            ref, tol = emu.dgrad(W.t(), eng.dZhist[i][t][:, :nc], x[:, :nc])
+            worst["dgrad"] = max(worst["dgrad"], _within(eng.dZhist[i - 1][t][:, :nc], ref, tol, f"layer {i}, period {t}: dgrad"))
+        # weight and bias gradient: the contraction over all periods (the gradient scale is inside dZhist: g_reward carries it, the
+        # slab reduction multiplies by 1)
+        ref, tol, ref_b, tol_b = emu.wgrad_periods(eng.dZhist[i][:, :, :n], eng.hidden[i - 1][:, :, :n])
+        worst["wgrad"] = max(worst["wgrad"], _within(grads[id(lins[i].weight)], ref, tol, f"layer {i}: weight gradient"),
+                             _within(grads[id(lins[i].bias)], ref_b, tol_b, f"layer {i}: bias gradient"))
+    # the ineligible layer 3 is the FP32 engine's arithmetic, bit for bit: bf16 mode changes nothing outside bf16_layers
+    assert 3 not in eng.Wb and 3 not in eng.Wtb
+    for t in range(T):
+        y = torch.full_like(eng.hidden[3][t], NAN)
+        ops.linear_fwd(eng.Wp[3][:, :288], lins[3].bias.detach(), eng.hidden[2][t], y, n, _lib.NIC_ACT_ELU)
+        assert torch.equal(y[:, :nc], eng.hidden[3][t][:, :nc]), f"layer 3, period {t}: not the FP32 kernel's output"
+    print(f"RATIO engine in place ({'graph replay' if graph else 'eager'}, {n} x T={T}, tail={eng._use_tail()}): "
+          + ", ".join(f"{k} {v:.4f}" for k, v in worst.items()))
