@@ -422,6 +422,14 @@ int nic_closed_form_num_partials(int32_t n_scenarios, int32_t S);
  * (Round 5: at 10^6 chains the reduction of `totals` took longer than the rollout.) */
 int nic_closed_form_rollout_sums(const NicClosedFormDesc* d, float* reward_hist, float* totals, float* state_final, float* partial,
                                  int32_t partial_stride, int32_t with_grad, int32_t with_sums, void* stream);
+/* Many candidate level vectors on the same demand trace in ONE launch (grid search, multi-start descent and cost landscapes of
+ * the closed-form baselines): candidate k runs the rollout above with levels[k * d->n_levels + j], and its numbers are those of
+ * nic_closed_form_rollout_sums with that row as d->levels bit for bit (with_sums = 1).  A lane advances a small group of
+ * candidates against each demand value it fetches.
+ * levels: device [n_candidates][d->n_levels] (d->levels is ignored); partial: [n_candidates][nic_closed_form_num_partials(B,S)][partial_stride],
+ * row = [d total/d level_j if with_grad][total, reported]; chain_totals: [n_candidates][2][S][ldb] or NULL (inspection). */
+int nic_closed_form_sweep(const NicClosedFormDesc* d, const float* levels, int32_t n_candidates, float* chain_totals,
+                          float* partial, int32_t partial_stride, int32_t with_grad, void* stream);
 
 /* ---- whole-horizon rollout of the data_driven policy for small batches (csrc/horizon_rollout.hip) --------------------
  * The reference trains DataDrivenNet (neural_networks.py:430-515, data_driven_net.yml: two 64-wide hidden layers) on batches of

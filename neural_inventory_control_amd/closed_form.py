@@ -157,6 +157,44 @@ class ClosedFormRollout:
         sums = partial.sum(dim=0)
         return sums[ng], sums[ng + 1], (sums[:ng] if want_grad else None)
 
+    def sweep(self, levels, data, periods, ignore_periods=0, observation_params=None, demand_soa=None, want_grad=True,
+              discrete_allocation=False):
+        """K candidate level vectors on one batch in ONE launch (grid search, multi-start descent, cost landscapes of the
+        baselines): `levels` [K, n_levels] in level space (a row = what `model.closed_form_levels()` returns) ->
+        plain tensors (total [K], reported [K], d total / d levels [K, n_levels] or None).  Row k carries the numbers of `run` with
+        those levels (per-chain values bit for bit; the last sum over wavefronts is one `partial.sum`).  Not differentiable."""
+        if discrete_allocation and want_grad:
+            raise ValueError("discrete_allocation is an evaluation-time option (rounded orders have zero gradient)")
+        prob = self._probs.get(self.problem_params, data, self.device)
+        if not supports_shapes(self.name, prob):
+            raise ValueError(f"{self.name}: setting outside the fused closed-form kernel (see nic_rollout.h)")
+        n_levels = {"base_stock": 1, "capped_base_stock": 2}.get(self.name, prob.E + 2)
+        if levels.dim() != 2 or levels.shape[0] < 1 or levels.shape[1] != n_levels:
+            raise ValueError(f"{self.name}: levels must be [K >= 1, {n_levels}] (got {tuple(levels.shape)})")
+        T, ld = periods, prob.ldb
+        self._setup(prob, T)
+        self.prob = prob
+        shift = observation_params["demand"]["period_shift"] if observation_params else 0
+        if demand_soa is None:
+            demand_soa = demand_trace_soa(data["demands"], ld, self.device)
+        if demand_soa.shape[0] < T + shift:
+            raise ValueError("Current period is greater than the number of periods in the data")
+        pack_state0(data, prob, self.state0)
+        lv = levels.detach().to(self.device, torch.float32).contiguous()
+        K = lv.shape[0]
+        desc = make_desc(prob, self.name, T, shift, ignore_periods, lv[0], demand_soa, self.state0, bool(discrete_allocation))
+        ng = n_levels if want_grad else 0
+        partial = torch.empty(K, self.n_partials, ng + 2, device=self.device)
+        self.sweep_totals = torch.zeros(K, 2, prob.S, ld, device=self.device) if self.keep_chain_totals else None
+        call = lambda: _lib.check(_lib.lib().nic_closed_form_sweep(  # noqa: E731
+            desc, _lib.ptr(lv), K, _lib.ptr(self.sweep_totals), _lib.ptr(partial), ng + 2, int(want_grad), _lib.current_stream()))
+        if self.timer is not None:
+            self.timer.call("closed_form_sweep", call)
+        else:
+            call()
+        sums = partial.sum(dim=1)
+        return sums[:, ng], sums[:, ng + 1], (sums[:, :ng] if want_grad else None)
+
     # ---- inspection helpers used by the parity tests ------------------------------------------------------------------
     def per_period_rewards(self):
         return self.rewards[:, :, :self.prob.B].sum(dim=1)

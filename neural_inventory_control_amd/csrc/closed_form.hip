@@ -52,9 +52,101 @@ __global__ __launch_bounds__(kBlock) void closed_form_kernel(NicClosedFormDesc d
     }
 }
 
-int validate(const NicClosedFormDesc* d) {
+// The sweep: lane = (chain, group of KC candidates), grid (ceil(B / 64), S, ceil(K / KC)).  Candidate k's row of `partial`
+// ([K][n_waves * S][partial_stride], row = [d total / d level_j ...][total, reported]) is what closed_form_kernel writes for a
+// launch with levels[k]: the same per-lane numbers through the same shuffle ladder.
+template <int NP, int MF, bool CHAIN, int WC, int KC>
+__global__ __launch_bounds__(kBlock) void closed_form_sweep_kernel(NicClosedFormDesc d, const float* __restrict__ levels,
+                                                                    int n_candidates, const float* __restrict__ demand,
+                                                                    const float* __restrict__ state0,
+                                                                    float* __restrict__ chain_totals, float* __restrict__ partial,
+                                                                    int partial_stride) {
+    const int64_t b = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int s = blockIdx.y;
+    const int k0 = blockIdx.z * KC;
+    d.demand = demand;
+    d.state0 = state0;
+    float g[KC][NP > 0 ? NP : 1];
+    float sums[KC][2];
+#pragma unroll
+    for (int i = 0; i < KC; ++i) {
+        sums[i][0] = sums[i][1] = 0.f;
+#pragma unroll
+        for (int j = 0; j < (NP > 0 ? NP : 1); ++j) g[i][j] = 0.f;
+    }
+    if (b < d.n_scenarios)
+        nic::closed_form_sweep_chain<NP, MF, CHAIN, WC, KC>(d, levels, n_candidates, k0, chain_totals, s, b, g, sums);
+    const int64_t wave_id = (int64_t)blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
+    const int64_t n_waves = (d.n_scenarios + kWave - 1) / kWave;
+    const bool writer = (threadIdx.x & (kWave - 1)) == 0 && wave_id < n_waves;
+#pragma unroll
+    for (int i = 0; i < KC; ++i) {
+        if (k0 + i >= n_candidates) break;   // (uniform over the workgroup)
+        float* row = partial + (((int64_t)(k0 + i) * d.S + blockIdx.y) * n_waves + wave_id) * partial_stride;
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            float v = g[i][j];
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+            if (writer) row[j] = v;
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            float v = sums[i][j];
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+            if (writer) row[NP + j] = v;
+        }
+    }
+}
+
+// Candidates per lane.  sweep_kc_fits: the largest group of 1 / 2 / 4 that compiles for gfx950 without scratch (register counts
+// per variant: DESIGN.md section 4).  sweep_kc: what is launched - measured at 32,768 chains x 100 periods, K = 16 and 64, a group of
+// 2 wins only for the forward-only single-store chains (one demand fetch and one set of statics for two cheap chains); with
+// tangents, and for the echelon chain, the grid's candidate dimension already fills the SIMDs and a wider lane only costs
+// occupancy, so those stay at 1.
+constexpr int sweep_kc_fits(int np, int mf, bool chain) {
+    if (!chain) return 4;                                  // single-store chains: <= 256 registers at 4 in every variant
+    if (np == 0) return mf <= 8 ? 4 : 2;                   // echelon chain, forward only
+    if (np == 3) return mf == 4 ? 4 : (mf == 8 ? 2 : 1);
+    return mf == 4 ? 2 : 1;                                // 4 and 5 tangents per slot
+}
+constexpr int sweep_kc(int np, int mf, bool chain) {
+#ifdef NIC_CF_SWEEP_TRY_KC   // (tuning builds: every variant at min(NIC_CF_SWEEP_TRY_KC, what fits); tools/closed_form_sweep.py --lib)
+    return sweep_kc_fits(np, mf, chain) < NIC_CF_SWEEP_TRY_KC ? sweep_kc_fits(np, mf, chain) : NIC_CF_SWEEP_TRY_KC;
+#else
+    return (!chain && np == 0 && mf == 4) ? 2 : 1;
+#endif
+}
+
+template <int NP, int MF, bool CHAIN, int WC>
+void launch_sweep(const NicClosedFormDesc* d, const float* levels, int n_candidates, float* chain_totals, float* partial,
+                  int partial_stride, hipStream_t s) {
+    constexpr int KC = sweep_kc(NP, MF, CHAIN);
+    const dim3 grid(nic::ceil_div(d->n_scenarios, kBlock), d->S, nic::ceil_div(n_candidates, KC)), block(kBlock);
+    nic::note_kernelf("closed_form_sweep_kernel<%d,%d,%s,%d,%d>", NP, MF, CHAIN ? "true" : "false", WC, KC);
+    hipLaunchKernelGGL((closed_form_sweep_kernel<NP, MF, CHAIN, WC, KC>), grid, block, 0, s, *d, levels, n_candidates, d->demand,
+                       d->state0, chain_totals, partial, partial_stride);
+}
+template <int MF, bool CHAIN, int WC>
+void launch_sweep_np(int np, const NicClosedFormDesc* d, const float* levels, int n_candidates, float* chain_totals,
+                     float* partial, int partial_stride, hipStream_t s) {
+#define NIC_CF_SWEEP(NP) launch_sweep<NP, MF, CHAIN, WC>(d, levels, n_candidates, chain_totals, partial, partial_stride, s)
+    if (np == 0) NIC_CF_SWEEP(0);
+    else if constexpr (CHAIN) {   // echelon_stock: E + 2 = 3..5 levels
+        if (np == 3) NIC_CF_SWEEP(3);
+        else if (np == 4) NIC_CF_SWEEP(4);
+        else NIC_CF_SWEEP(5);
+    } else {                      // base_stock: 1 level, capped_base_stock: 2
+        if (np == 1) NIC_CF_SWEEP(1);
+        else NIC_CF_SWEEP(2);
+    }
+#undef NIC_CF_SWEEP
+}
+
+int validate(const NicClosedFormDesc* d, const float* levels) {
     NIC_REQUIRE(d, "nic_closed_form_rollout: null descriptor");
-    NIC_REQUIRE(d->levels && d->demand && d->state0, "nic_closed_form_rollout: null levels / demand / state0");
+    NIC_REQUIRE(levels && d->demand && d->state0, "nic_closed_form_rollout: null levels / demand / state0");
     NIC_REQUIRE(d->n_scenarios > 0 && d->ldb >= d->n_scenarios && d->T > 0 && d->t0 >= 0 && d->S >= 1,
                 "nic_closed_form_rollout: bad sizes");
     NIC_REQUIRE(d->policy >= NIC_CF_BASE_STOCK && d->policy <= NIC_CF_ECHELON, "nic_closed_form_rollout: unknown policy %d", d->policy);
@@ -85,7 +177,7 @@ int nic_closed_form_num_partials(int32_t n_scenarios, int32_t S) {
 int nic_closed_form_rollout_sums(const NicClosedFormDesc* d, float* reward_hist, float* totals, float* state_final, float* partial,
                                  int32_t partial_stride, int32_t with_grad, int32_t with_sums, void* stream) {
     float* g_levels_partial = with_grad ? partial : nullptr;
-    if (int e = validate(d)) return e;
+    if (int e = validate(d, d ? d->levels : nullptr)) return e;
     NIC_REQUIRE(!(d->round_orders && g_levels_partial), "nic_closed_form_rollout: rounded orders have no gradient");
     NIC_REQUIRE(!(with_grad || with_sums) || (partial && partial_stride >= (with_grad ? d->n_levels : 0) + (with_sums ? 2 : 0)),
                 "nic_closed_form_rollout: partial buffer missing or its rows too short");
@@ -146,5 +238,36 @@ int nic_closed_form_rollout_sums(const NicClosedFormDesc* d, float* reward_hist,
     }
 #undef NIC_CF_LAUNCH
     return nic::check_launch("nic_closed_form_rollout");
+}
+
+int nic_closed_form_sweep(const NicClosedFormDesc* d, const float* levels, int32_t n_candidates, float* chain_totals,
+                          float* partial, int32_t partial_stride, int32_t with_grad, void* stream) {
+    if (int e = validate(d, levels)) return e;
+    NIC_REQUIRE(n_candidates >= 1, "nic_closed_form_sweep: needs at least one candidate (got %d)", n_candidates);
+    NIC_REQUIRE(n_candidates <= 65535, "nic_closed_form_sweep: at most 65535 candidates per launch (got %d)", n_candidates);
+    NIC_REQUIRE(!(d->round_orders && with_grad), "nic_closed_form_sweep: rounded orders have no gradient");
+    NIC_REQUIRE(partial && partial_stride >= (with_grad ? d->n_levels : 0) + 2,
+                "nic_closed_form_sweep: partial buffer missing or its rows too short");
+    hipStream_t s = nic::as_stream(stream);
+    // the variant is chosen as for the single launch (nic_closed_form_rollout_sums)
+    const int np = with_grad ? d->n_levels : 0;
+    const bool chain = d->policy == NIC_CF_ECHELON;
+    int w = d->Ws;
+    if (chain) w = w > d->Ww ? w : d->Ww, w = w > d->We ? w : d->We;
+    const int mf = w <= 4 ? 4 : (w <= 8 ? 8 : 16);
+    const int wc = (!chain && mf == 4 && d->lead.scn_stride == 0) ? d->Ws : 0;
+#define NIC_CF_SWEEP(MF, CH, WCV) launch_sweep_np<MF, CH, WCV>(np, d, levels, n_candidates, chain_totals, partial, partial_stride, s)
+    if (chain) {
+        if (mf == 4) NIC_CF_SWEEP(4, true, 0);
+        else if (mf == 8) NIC_CF_SWEEP(8, true, 0);
+        else NIC_CF_SWEEP(16, true, 0);
+    } else if (wc == 2) NIC_CF_SWEEP(4, false, 2);
+    else if (wc == 3) NIC_CF_SWEEP(4, false, 3);
+    else if (wc == 4) NIC_CF_SWEEP(4, false, 4);
+    else if (mf == 4) NIC_CF_SWEEP(4, false, 0);
+    else if (mf == 8) NIC_CF_SWEEP(8, false, 0);
+    else NIC_CF_SWEEP(16, false, 0);
+#undef NIC_CF_SWEEP
+    return nic::check_launch("nic_closed_form_sweep");
 }
 }

@@ -474,6 +474,23 @@ NIC_HD void cf_pipe_store(const CfPipe<NP, MW>& p, float* dst, int W, int64_t ld
         if (k < W) dst[(int64_t)k * ldb] = p.s[k].v;
 }
 
+// initial pipelines of chain (store s, scenario b) with zero tangents, and every pipeline's landing slot
+template <int NP, int MW, bool CHAIN>
+NIC_HD void cf_state_load(const NicClosedFormDesc& d, const CfStatics& c, int s, int64_t b, CfState<NP, MW, CHAIN>& st) {
+    const int64_t ldb = d.ldb;
+    const int F = d.Ws + d.Wn * d.Ww + d.E * d.We;
+    const float* s0 = d.state0 + (int64_t)s * F * ldb + b;
+    cf_pipe_load(st.store, s0, d.Ws, ldb);
+    cf_pipe_load(st.wh, s0 + (int64_t)d.Ws * ldb, CHAIN ? d.Ww : 0, ldb);
+#pragma unroll
+    for (int e = 0; e < (CHAIN ? CF_MAXE : 1); ++e)
+        cf_pipe_load(st.ech[e], s0 + (int64_t)(d.Ws + d.Ww + e * d.We) * ldb, (CHAIN && e < d.E) ? d.We : 0, ldb);
+    cf_pipe_set_lead(st.store, c.lead);
+    cf_pipe_set_lead(st.wh, c.wh_lead);
+#pragma unroll
+    for (int e = 0; e < (CHAIN ? CF_MAXE : 1); ++e) cf_pipe_set_lead(st.ech[e], c.e_lead[e < CF_MAXE ? e : 0]);
+}
+
 // Whole horizon of chain (store s, scenario b).  MW = register slots per pipeline (>= every live pipeline length).
 // Outputs (each may be NULL):
 //   reward_hist [T][S][ldb]   per-period cost of this chain
@@ -523,16 +540,7 @@ NIC_HD void closed_form_chain(const NicClosedFormDesc& d, float* reward_hist, fl
 #pragma unroll
     for (int j = 0; j < NIC_CF_MAX_LEVELS; ++j) lv[j] = j < d.n_levels ? dparam<NP>(d.levels[j], j) : dconst<NP>(0.f);
     CfState<NP, MW, CHAIN> st;
-    const float* s0 = d.state0 + (int64_t)s * F * ldb + b;
-    cf_pipe_load(st.store, s0, d.Ws, ldb);
-    cf_pipe_load(st.wh, s0 + (int64_t)d.Ws * ldb, CHAIN ? d.Ww : 0, ldb);
-#pragma unroll
-    for (int e = 0; e < (CHAIN ? CF_MAXE : 1); ++e)
-        cf_pipe_load(st.ech[e], s0 + (int64_t)(d.Ws + d.Ww + e * d.We) * ldb, (CHAIN && e < d.E) ? d.We : 0, ldb);
-    cf_pipe_set_lead(st.store, c.lead);
-    cf_pipe_set_lead(st.wh, c.wh_lead);
-#pragma unroll
-    for (int e = 0; e < (CHAIN ? CF_MAXE : 1); ++e) cf_pipe_set_lead(st.ech[e], c.e_lead[e < CF_MAXE ? e : 0]);
+    cf_state_load(d, c, s, b, st);
     Dual<NP> total = dconst<NP>(0.f);
     float reported = 0.f;
     const float* dem_p = d.demand + ((int64_t)d.t0 * d.S + s) * ldb + b;
@@ -582,6 +590,106 @@ NIC_HD void closed_form_chain(const NicClosedFormDesc& d, float* reward_hist, fl
     }
 #pragma unroll
     for (int j = 0; j < NP; ++j) g[j] = total.d.get(j);
+}
+
+// ---- sweep: KC candidate level vectors per lane -----------------------------------------------------------------------------
+// One lane owns (chain, group of KC candidates): the chain's statics, initial pipelines and demand are fetched once and KC
+// independent states advance against each demand value - KC dependency chains per lane where closed_form_chain has one (its
+// period is latency-bound).  Every candidate runs closed_form_chain's operations in closed_form_chain's order (the same
+// cf_policy / cf_env_step instantiations, the same accumulation), so its numbers are those of a single-candidate run bit for bit.
+template <int NP, int MW, bool CHAIN, int WC, int FL, int KC>
+NIC_HD void cf_sweep_horizon(const NicClosedFormDesc& d, const CfStatics& c, const Dual<NP> (&lv)[KC][NIC_CF_MAX_LEVELS],
+                             CfState<NP, MW, CHAIN> (&st)[KC], const float* dem_p, int64_t dem_stride, int uniform_slot,
+                             Dual<NP> (&total)[KC], float (&reported)[KC]) {
+    float cur[kCfAhead], nxt[kCfAhead];
+#pragma unroll
+    for (int j = 0; j < kCfAhead; ++j) cur[j] = dem_p[(int64_t)(j < d.T ? j : d.T - 1) * dem_stride];
+    for (int t0 = 0; t0 < d.T; t0 += kCfAhead) {
+#pragma unroll
+        for (int j = 0; j < kCfAhead; ++j) {
+            const int tn = t0 + kCfAhead + j;
+            nxt[j] = dem_p[(int64_t)(tn < d.T ? tn : d.T - 1) * dem_stride];
+        }
+#pragma unroll
+        for (int j = 0; j < kCfAhead; ++j) {
+            const int t = t0 + j;
+            if (t < d.T) {
+#pragma unroll
+                for (int i = 0; i < KC; ++i) {
+                    const CfOrders<NP> o = cf_policy<NP, MW, CHAIN, WC, FL>(d, lv[i], st[i]);
+                    const Dual<NP> r = cf_env_step<NP, MW, CHAIN, WC, FL>(d, c, st[i], cur[j], o, uniform_slot);
+                    total[i] = total[i] + r;
+                    if (t >= d.ignore_periods) reported[i] += r.v;
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kCfAhead; ++j) cur[j] = nxt[j];
+    }
+}
+
+// Whole horizon of chain (store s, scenario b) under candidates k0 .. k0 + KC - 1 of levels [n_candidates][d.n_levels] (d.levels
+// is not read).  A slot past n_candidates recomputes the last candidate and writes nothing.  Outputs:
+//   chain_totals [n_candidates][2][S][ldb] (may be NULL)   closed_form_chain's `totals`, per candidate
+//   g [KC][NP], sums [KC][2]                               closed_form_chain's `g` and `chain_sums`, per slot
+template <int NP, int MW, bool CHAIN, int WC, int KC>
+NIC_HD void closed_form_sweep_chain(const NicClosedFormDesc& d, const float* levels, int n_candidates, int k0, float* chain_totals,
+                                    int s, int64_t b, float (&g)[KC][NP > 0 ? NP : 1], float (&sums)[KC][2]) {
+    const int64_t ldb = d.ldb;
+    const CfStatics c = cf_load_statics(d, s, b);
+    Dual<NP> lv[KC][NIC_CF_MAX_LEVELS];
+    CfState<NP, MW, CHAIN> st[KC];
+    cf_state_load(d, c, s, b, st[0]);
+#pragma unroll
+    for (int i = 0; i < KC; ++i) {
+        const int k = k0 + i < n_candidates ? k0 + i : n_candidates - 1;
+#pragma unroll
+        for (int j = 0; j < NIC_CF_MAX_LEVELS; ++j)
+            lv[i][j] = j < d.n_levels ? dparam<NP>(levels[(int64_t)k * d.n_levels + j], j) : dconst<NP>(0.f);
+        if (i > 0) st[i] = st[0];
+    }
+    Dual<NP> total[KC];
+    float reported[KC];
+#pragma unroll
+    for (int i = 0; i < KC; ++i) {
+        total[i] = dconst<NP>(0.f);
+        reported[i] = 0.f;
+    }
+    const float* dem_p = d.demand + ((int64_t)d.t0 * d.S + s) * ldb + b;
+    const int64_t dem_stride = (int64_t)d.S * ldb;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const int uniform_slot = WC > 0 ? __builtin_amdgcn_readfirstlane((int)c.lead - 1) : -2;
+#else
+    const int uniform_slot = WC > 0 ? (int)c.lead - 1 : -2;
+#endif
+#define NIC_CF_RUN(FLV) cf_sweep_horizon<NP, MW, CHAIN, WC, FLV, KC>(d, c, lv, st, dem_p, dem_stride, uniform_slot, total, reported)
+    if (WC > 0) {
+        switch ((d.round_orders ? 1 : 0) | (d.lost_demand ? 2 : 0) | (d.maximize_profit ? 4 : 0)) {
+            case 0: NIC_CF_RUN(0); break;
+            case 1: NIC_CF_RUN(1); break;
+            case 2: NIC_CF_RUN(2); break;
+            case 3: NIC_CF_RUN(3); break;
+            case 4: NIC_CF_RUN(4); break;
+            case 5: NIC_CF_RUN(5); break;
+            case 6: NIC_CF_RUN(6); break;
+            default: NIC_CF_RUN(7); break;
+        }
+    } else {
+        NIC_CF_RUN(-1);
+    }
+#undef NIC_CF_RUN
+#pragma unroll
+    for (int i = 0; i < KC; ++i) {
+        if (chain_totals && k0 + i < n_candidates) {
+            float* t = chain_totals + (int64_t)(k0 + i) * 2 * d.S * ldb;
+            t[(int64_t)s * ldb + b] = total[i].v;
+            t[((int64_t)d.S + s) * ldb + b] = reported[i];
+        }
+        sums[i][0] = total[i].v;
+        sums[i][1] = reported[i];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) g[i][j] = total[i].d.get(j);
+    }
 }
 
 }  // namespace nic

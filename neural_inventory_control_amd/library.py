@@ -8,6 +8,8 @@
                                                        the warehouse policies' feasibility head on csrc/policy_heads.hip
     nic::rollout_closed_form(levels, demand, state0, problem, policy, T, t0, ignore, round) -> (total, reported, d total / d levels)
                                                        whole horizon of a closed-form policy on csrc/closed_form.hip
+    nic::sweep_closed_form(levels [K, L], demand, state0, problem, policy, T, t0, ignore, round, want_grad) -> (total [K], reported [K],
+                                                       d total / d levels [K, L]): K candidate level vectors in one launch (not differentiable)
     nic::sample_demand(mean, std?, rho, T, n, offset, seed, clip, poisson) -> demand [T][S][ldb]
                                                        the batched demand sampler on csrc/sampler.hip (not differentiable)
 
@@ -318,6 +320,36 @@ def _cf_backward(ctx, g_total, g_reported, g_glevels):
 
 
 rollout_closed_form.register_autograd(_cf_backward, setup_context=_cf_setup)
+
+
+# ---- nic::sweep_closed_form: K candidate level vectors of a closed-form policy in one launch ---------------------------------------
+
+@torch.library.custom_op("nic::sweep_closed_form", mutates_args=())
+def sweep_closed_form(levels: torch.Tensor, demand: torch.Tensor, state0: torch.Tensor, problem: int, policy: int, periods: int,
+                      first_period: int, ignore_periods: int, round_orders: bool,
+                      want_grad: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """`nic::rollout_closed_form` for K candidate level vectors at once (`nic_closed_form_sweep`): levels [K][n_levels] ->
+    (total [K], reported [K], d total / d levels [K][n_levels], zeros without `want_grad`).  A search tool's operator: it has NO
+    autograd formula (the level gradient is an output, not a backward)."""
+    from . import closed_form
+    prob = _PROBLEMS[problem]
+    name = {v: k for k, v in closed_form.POLICY_ID.items()}[policy]
+    lv = levels.detach().float().contiguous()
+    K, L = lv.shape
+    desc = closed_form.make_desc(prob, name, periods, first_period, ignore_periods, lv[0], demand, state0, round_orders)
+    ng = L if want_grad else 0
+    partial = torch.empty(K, _lib.lib().nic_closed_form_num_partials(prob.B, prob.S), ng + 2, device=levels.device)
+    _lib.check(_lib.lib().nic_closed_form_sweep(desc, _lib.ptr(lv), K, None, _lib.ptr(partial), ng + 2, int(want_grad),
+                                                _lib.current_stream()))
+    sums = partial.sum(dim=1)
+    return sums[:, ng].clone(), sums[:, ng + 1].clone(), (sums[:, :ng].clone() if ng else torch.zeros_like(lv))
+
+
+@sweep_closed_form.register_fake
+def _(levels, demand, state0, problem, policy, periods, first_period, ignore_periods, round_orders, want_grad):
+    K = levels.shape[0]
+    return (levels.new_empty((K,), dtype=torch.float32), levels.new_empty((K,), dtype=torch.float32),
+            levels.new_empty(levels.shape, dtype=torch.float32))
 
 
 # ---- nic::sample_demand: the batched demand sampler ------------------------------------------------------------------------------
