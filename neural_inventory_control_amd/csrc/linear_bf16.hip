@@ -25,6 +25,7 @@
 // No atomics (every slab element has one owner workgroup: results are deterministic run to run); no inline asm.
 #include "nic_common.h"
 #include "nic_bf16.h"
+#include "wgrad_plan.h"
 
 namespace {
 
@@ -335,20 +336,6 @@ __global__ __launch_bounds__(kThreads) void bf16_wgrad_kernel(WgParams p) {
     }
 }
 
-// the slot factorisation of nic_linear_wgrad_periods (linear_mfma.hip): scenario chunks down to 128 scenarios, the rest of the
-// slots split the horizon into period groups
-void period_factors(int n_slots, int n_scenarios, int n_periods, int* scen_splits, int* groups) {
-    int cap = n_scenarios / 128;
-    if (cap < 1) cap = 1;
-    int ss = n_slots < cap ? n_slots : cap;
-    if (ss < 1) ss = 1;
-    int g = n_slots / ss;
-    if (g > n_periods) g = n_periods;
-    if (g < 1) g = 1;
-    *scen_splits = ss;
-    *groups = g;
-}
-
 bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 template <int EPI>
@@ -365,8 +352,9 @@ int launch_wx(const WxParams& p, hipStream_t s) {
     return 0;
 }
 
+// period_groups: slots are (scenario split, period group) pairs, else scenario splits; factors, chunk and flush: wgrad_plan.h
 int wgrad_bf16(const float* dY, const float* X, float* slab, int64_t lds_, int32_t N, int32_t K, int32_t n_scenarios, int32_t ldb,
-               int32_t n_slots, int32_t n_periods, int64_t pstride_dy, int64_t pstride_x, int scen_splits, int groups, void* stream,
+               int32_t n_slots, int32_t n_periods, int64_t pstride_dy, int64_t pstride_x, bool period_groups, void* stream,
                const char* who) {
     NIC_REQUIRE(dY && X && slab, "%s: null buffer", who);
     NIC_REQUIRE(nic_linear_bf16_ok(N, K), "%s: N and K must be multiples of 32 and >= 128 (%d x %d)", who, N, K);
@@ -375,14 +363,14 @@ int wgrad_bf16(const float* dY, const float* X, float* slab, int64_t lds_, int32
                 who, ldb, n_scenarios);
     NIC_REQUIRE(aligned16(dY) && aligned16(X) && pstride_dy % 4 == 0 && pstride_x % 4 == 0,
                 "%s: dY / X must be 16-byte aligned (period strides multiples of 4 elements)", who);
-    int chunk = (n_scenarios + scen_splits - 1) / scen_splits;
-    chunk = (chunk + BK - 1) / BK * BK;
-    const int ppg = (n_periods + groups - 1) / groups;
-    const int flush = 8192 / chunk > 0 ? 8192 / chunk : 1;
-    WgParams p{dY, X, slab, lds_, ldb, N, K, n_scenarios, chunk, n_periods, pstride_dy, pstride_x, flush, scen_splits, ppg};
+    const nic::WgradSlots slots = period_groups ? nic::period_factors(n_slots, n_scenarios, n_periods)
+                                                : nic::scenario_slots(n_slots, n_scenarios, n_periods);
+    WgParams p{dY, X, slab, lds_, ldb, N, K, n_scenarios, slots.chunk, n_periods, pstride_dy, pstride_x,
+               nic::wgrad_flush_periods(slots.chunk), slots.scen_splits, slots.periods_per_group};
     const int tiles = ((N + 127) / 128) * ((K + 127) / 128);
     nic::note_kernel("bf16_wgrad_kernel<2,2>");
-    hipLaunchKernelGGL((bf16_wgrad_kernel<2, 2>), dim3(tiles * scen_splits * groups), dim3(kThreads), 0, nic::as_stream(stream), p);
+    hipLaunchKernelGGL((bf16_wgrad_kernel<2, 2>), dim3(tiles * slots.scen_splits * slots.groups), dim3(kThreads), 0,
+                       nic::as_stream(stream), p);
     return nic::check_launch(who);
 }
 
@@ -423,7 +411,7 @@ int nic_linear_bf16_dgrad(const uint16_t* Wt, int64_t ldwt, const float* dY, con
 
 int nic_linear_bf16_wgrad(const float* dY, const float* X, float* slab, int64_t lds_, int32_t N, int32_t K, int32_t n_scenarios,
                           int32_t ldb, int32_t n_splits, void* stream) {
-    return wgrad_bf16(dY, X, slab, lds_, N, K, n_scenarios, ldb, n_splits, 1, 0, 0, n_splits, 1, stream, "nic_linear_bf16_wgrad");
+    return wgrad_bf16(dY, X, slab, lds_, N, K, n_scenarios, ldb, n_splits, 1, 0, 0, false, stream, "nic_linear_bf16_wgrad");
 }
 
 int nic_linear_bf16_wgrad_periods(const float* dY, const float* X, float* slab, int64_t lds_, int32_t N, int32_t K,
@@ -437,9 +425,7 @@ int nic_linear_bf16_wgrad_periods(const float* dY, const float* X, float* slab, 
         period_stride_dy = -period_stride_dy;
         period_stride_x = -period_stride_x;
     }
-    int ss, groups;
-    period_factors(n_splits, n_scenarios, n_periods, &ss, &groups);
-    return wgrad_bf16(dY, X, slab, lds_, N, K, n_scenarios, ldb, n_splits, n_periods, period_stride_dy, period_stride_x, ss, groups,
+    return wgrad_bf16(dY, X, slab, lds_, N, K, n_scenarios, ldb, n_splits, n_periods, period_stride_dy, period_stride_x, true,
                       stream, "nic_linear_bf16_wgrad_periods");
 }
 }

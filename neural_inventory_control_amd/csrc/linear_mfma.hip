@@ -25,12 +25,14 @@
 //             free because parity is defined to 1e-5, not bitwise, for the policy GEMMs.
 // Fallback kernels (gemm_wx_kernel, gemm_wgrad_kernel): register-staged, per-element guards, for unaligned operands,
 // scenario counts that are not a multiple of 32, and the thin layers of the weight gradient.
+// Dispatch: forward / dgrad in dispatch_wx below; the weight gradient (kernel, slab slots, chunk, flush, launches) in wgrad_plan.h.
 // Roofline: MFMA-bound.  Measured on MI355X (512 x 512 x 65,536): 102-114 TFLOP/s; MFMA pipe 70 % busy at a 2.26 GHz
 // sustained clock (profiles/r01_gemm_pmc_dma256.txt); the remainder is the per-tile DMA wait + barrier (a no-DMA timing
 // build runs 117 TFLOP/s) and the unoverlapped prologue / epilogue of a 1-workgroup-per-CU kernel.
 #include <stdlib.h>
 
 #include "nic_common.h"
+#include "wgrad_plan.h"
 
 namespace {
 
@@ -1433,82 +1435,37 @@ void dispatch_wx(const WxParams& p, hipStream_t s) {
     else launch_wx<1, 4, 1, 2, EPI>(p, s);
 }
 
+// ---- weight gradient: launches.  WHICH kernel runs, over which slots, is decided in wgrad_plan.h ----------------------------------
 template <int WM, int WN, int MT, int NT>
-void launch_wg(const WgParams& p, int n_splits, hipStream_t s) {
+void launch_wg(const WgParams& p, int n_splits, bool fast, hipStream_t s) {
     constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
     dim3 grid(((p.K + 1 + BN - 1) / BN) * ((p.N + BM - 1) / BM) * n_splits);
-    const bool fast = p.ldb % 4 == 0 && (reinterpret_cast<uintptr_t>(p.dY) & 15) == 0 &&
-                      (reinterpret_cast<uintptr_t>(p.X) & 15) == 0 && (int64_t)p.N * p.ldb < (1ll << 28) &&
-                      (int64_t)p.K * p.ldb < (1ll << 28);
     nic::note_kernelf("gemm_wgrad_kernel<%d,%d,%d,%d,%d>", WM, WN, MT, NT, fast ? 1 : 0);
     if (fast) hipLaunchKernelGGL((gemm_wgrad_kernel<WM, WN, MT, NT, 1>), grid, dim3(kThreads), 0, s, p);
     else hipLaunchKernelGGL((gemm_wgrad_kernel<WM, WN, MT, NT, 0>), grid, dim3(kThreads), 0, s, p);
 }
 
-// the tile shape is a function of (N, K) only so that nic_wgrad_num_splits and the launch agree
-void wgrad_tile(int N, int K, int* bm, int* bn) {
-    if (N > 64) { *bm = 128; *bn = (K + 1 > 64) ? 128 : 64; }
-    else if (N > 32) { *bm = 64; *bn = 128; }
-    else { *bm = 32; *bn = 256; }
-}
-
-// big layers: 256 x 256 LDS-DMA tiles, one workgroup per CU
-bool wgrad_big(int N, int K) { return N >= 192 && K >= 129; }
-// N >= 192 output rows over 65..128 input rows (the shipped many-warehouse setting's first layer: 512 x 66): 256 x 128 tiles on
-// the LDS-DMA pipeline (round 4; the register-staged 128 x 128 kernel ran that layer's all-period gradient at 0.02 of peak)
-bool wgrad_half(int N, int K) { return N >= 192 && K > 64 && K <= 128; }
-bool wgrad_dma_shape(int N, int K);
-bool wgrad_tall(int N, int K);
-bool wgrad_wide(int N, int K);
-bool wgrad_mid(int N, int K);
-
-// tall, narrow layers (the first layer: 512 x 51): ONE 512 x 64 output tile per scenario chunk, so dZ is read exactly once
-// (the 128 x 64 register-staged tiles read it 1.3 x) by the LDS-DMA pipeline; HBM-bound
-bool wgrad_tall(int N, int K) { return N >= 384 && K <= 64; }
-
 template <int WM, int WN, int MT, int NT, bool SKIP = false>
-void launch_wg_dma(const WgParams& p, int n_splits, hipStream_t s) {
+void launch_wg_dma(const WgParams& p, int n_splits, bool, hipStream_t s) {
     constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
     dim3 grid(((p.K + BN - 1) / BN) * ((p.N + BM - 1) / BM) * n_splits);
     nic::note_kernelf(SKIP ? "gemm_wgrad_dma_kernel<%d,%d,%d,%d,skip>" : "gemm_wgrad_dma_kernel<%d,%d,%d,%d>", WM, WN, MT, NT);
     hipLaunchKernelGGL((gemm_wgrad_dma_kernel<WM, WN, MT, NT, SKIP>), grid, dim3(64 * WM * WN), 0, s, p);
 }
-// K in (256, 448] (cfg5's first layer: 393 input rows, 295 of them live): ONE 320 / 384 / 448-column tile covers it (88 % of the
-// tile's columns used at K = 393) where two 256-column tiles compute 512 (77 %); 128 x 448 keeps the 112 accumulator registers
-// of the 7-tile wx kernel
-bool wgrad_wide(int N, int K) { return wgrad_big(N, K) && K > 256 && K <= 448 && N % 128 == 0; }
-int wgrad_wide_nt(int K) { return (K + 63) / 64; }   // 5, 6 or 7 column tiles of 32 per wave column: 320 / 384 / 448 columns
 
-// 96 <= N <= 128 output rows over a wide input (cfg5's compacted logits layer, 98 x 512): 128 x 256 tiles on the LDS-DMA pipeline
-// (the register-staged 128 x 128 kernel reaches 0.37 of peak there)
-bool wgrad_mid(int N, int K) { return N >= 96 && N <= 128 && K >= 192; }
-
-bool wgrad_dma_shape(int N, int K) { return wgrad_big(N, K) || wgrad_tall(N, K) || wgrad_mid(N, K) || wgrad_half(N, K); }
-// output tiles of one scenario chunk under the LDS-DMA kernel launch_wg_dma_for picks (what the split counts divide 256 by)
-int wgrad_dma_tiles(int N, int K) {
-    if (wgrad_tall(N, K)) return (N + 511) / 512;
-    if (wgrad_half(N, K)) return (N + 255) / 256;
-    if (wgrad_mid(N, K)) return (K + 255) / 256;
-    if (wgrad_wide(N, K)) return (N + 127) / 128;
-    return ((N + 127) / 128) * ((K + 255) / 256);
+template <int KC>
+void launch_wg_small(const WgParams& p, int n_splits, bool, hipStream_t s) {
+    nic::note_kernelf("wgrad_small_kernel<%d>", KC);
+    hipLaunchKernelGGL(wgrad_small_kernel<KC>, dim3((n_splits + 3) / 4), dim3(kThreads), 0, s, p, n_splits);
 }
 
-// the LDS-DMA weight-gradient kernel for a shape (wgrad_dma_shape)
-void launch_wg_dma_for(const WgParams& p, int n_splits, hipStream_t s) {
-    if (wgrad_tall(p.N, p.K)) launch_wg_dma<8, 1, 2, 2>(p, n_splits, s);
-    else if (wgrad_half(p.N, p.K)) launch_wg_dma<4, 2, 2, 2>(p, n_splits, s);
-    else if (wgrad_mid(p.N, p.K)) launch_wg_dma<2, 4, 2, 2>(p, n_splits, s);
-    else if (wgrad_wide(p.N, p.K)) {
-        const int nt = wgrad_wide_nt(p.K);
-        if (nt == 5) launch_wg_dma<4, 2, 1, 5>(p, n_splits, s);
-        else if (nt == 6) launch_wg_dma<4, 2, 1, 6>(p, n_splits, s);
-        else launch_wg_dma<4, 2, 1, 7>(p, n_splits, s);
-    }
-    // big layers: 128 x 256 tiles (round 4; wave tile 64 x 64 = 64 accumulator registers, no scratch).  Measured against round 3's
-    // 256 x 256 tile (128 accumulators, 516 B of scratch) on 512 x 512 x 16,384 x T=50: 133.3-133.9 against 131.8 TFLOP/s
-    // (profiles/r04_gemm_stagger_and_wgrad_tile_probe.json)
-    else launch_wg_dma<2, 4, 2, 2>(p, n_splits, s);
-}
+// the instantiation behind every nic::WgradTile, in the enum's order
+void (*const kWgLaunch[])(const WgParams&, int n_splits, bool fast, hipStream_t) = {
+    launch_wg_small<1>, launch_wg_small<2>, launch_wg_small<3>, launch_wg_small<4>,
+    launch_wg_dma<8, 1, 2, 2>, launch_wg_dma<4, 2, 2, 2>, launch_wg_dma<2, 4, 2, 2>,                              // tall, half, mid
+    launch_wg_dma<4, 2, 1, 5>, launch_wg_dma<4, 2, 1, 6>, launch_wg_dma<4, 2, 1, 7>, launch_wg_dma<2, 4, 2, 2>,   // wide 5-7, big
+    launch_wg<2, 2, 2, 2>, launch_wg<2, 2, 2, 1>, launch_wg<1, 4, 2, 1>, launch_wg<1, 4, 1, 2>};
+static_assert(sizeof(kWgLaunch) / sizeof(kWgLaunch[0]) == nic::WG_STAGED_32x256 + 1, "one launcher per nic::WgradTile");
 
 int require_ld(const char* who, int32_t n_scenarios, int32_t ldb) {
     NIC_REQUIRE(n_scenarios > 0 && ldb >= n_scenarios && ldb % 4 == 0, "%s: ldb (%d) must be a multiple of 4 and >= n_scenarios (%d)",
@@ -1547,109 +1504,39 @@ int nic_linear_dgrad(const float* Wt, int64_t ldwt, const float* dY, const float
 }
 
 int nic_wgrad_num_splits(int32_t N, int32_t K, int32_t n_scenarios) {
-    if (N <= 0 || K <= 0 || n_scenarios <= 0) return 0;
-    int bm, bn;
-    wgrad_tile(N, K, &bm, &bn);
-    int tiles = ((N + bm - 1) / bm) * ((K + 1 + bn - 1) / bn);
-    int target = 4 * nic::cu_count();                  // ~4 workgroups per CU in total
-    if (wgrad_dma_shape(N, K)) {                       // LDS-DMA tiles, one workgroup per CU, one round
-        tiles = wgrad_dma_tiles(N, K);
-        target = nic::cu_count();
-    }
-    if (N <= 32 && (K <= 32 || (K <= 128 && K % 32 != 0))) {  // wgrad_small_kernel: one split per wave, >= 2048 columns each
-        int sp = (int)(((int64_t)n_scenarios + 2047) / 2048);
-        if (sp > 1024) sp = 1024;  // one wave per SIMD
-        return (sp + 3) / 4 * 4;
-    }
-    if (N <= NIC_THIN_MAX_ROWS && K % 32 == 0) {  // nic_linear_bwd_thin: one wave per (split, 32-row chunk), 2 waves per SIMD
-        int sp = 2048 / (K / 32);
-        const int cap = (n_scenarios + 63) / 64;  // at least one 64-scenario block per split
-        if (sp > cap) sp = cap;
-        return sp < 1 ? 1 : sp;
-    }
-    int splits = (target + tiles - 1) / tiles;
-    const int max_splits = (n_scenarios + 255) / 256;  // at least 256 scenarios (8 k-tiles) per split
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    return splits;
+    return nic::wgrad_recommended_slots(N, K, n_scenarios, nic::cu_count());
 }
-
-// Slab slots of the all-period contraction (nic_linear_wgrad_periods) as (scenario splits x period groups): scenario chunks go
-// down to 128 scenarios (4 k tiles per period), what is still missing to fill the chip comes from splitting the horizon.
-static void wgrad_period_factors(int32_t n_slots, int32_t n_scenarios, int32_t n_periods, int* scen_splits, int* groups) {
-    int cap = n_scenarios / 128;
-    if (cap < 1) cap = 1;
-    int ss = n_slots < cap ? n_slots : cap;
-    if (ss < 1) ss = 1;
-    int g = n_slots / ss;
-    if (g > n_periods) g = n_periods;
-    if (g < 1) g = 1;
-    *scen_splits = ss;
-    *groups = g;
-}
-
 int nic_wgrad_periods_num_splits(int32_t N, int32_t K, int32_t n_scenarios, int32_t n_periods) {
-    if (N <= 0 || K <= 0 || n_scenarios <= 0 || n_periods <= 0) return 0;
-    if (N <= 32 && K <= 32) return nic_wgrad_num_splits(N, K, n_scenarios);   // wgrad_small_kernel: one launch per period
-    if (!wgrad_dma_shape(N, K) || n_scenarios % BK != 0) {
-        // register-staged kernels (ragged scenario counts, narrow layers: the real-data batches of 72-288 products x 95 weeks):
-        // the same (period group x scenario split) slots - ONE launch instead of a serial walk over the horizon by 1-4 workgroups
-        int bm, bn;
-        wgrad_tile(N, K, &bm, &bn);
-        const int tiles = ((N + bm - 1) / bm) * ((K + 1 + bn - 1) / bn);
-        int ss, g;
-        wgrad_period_factors((4 * nic::cu_count() + tiles - 1) / tiles, n_scenarios, n_periods, &ss, &g);
-        const int base = nic_wgrad_num_splits(N, K, n_scenarios);
-        return ss * g > base ? ss * g : base;
-    }
-    const int tiles = wgrad_dma_tiles(N, K);
-    const int slots = (nic::cu_count() + tiles - 1) / tiles;   // one workgroup per CU, one round
-    int ss, g;
-    wgrad_period_factors(slots, n_scenarios, n_periods, &ss, &g);
-    return ss * g;
+    return nic::wgrad_periods_recommended_slots(N, K, n_scenarios, n_periods, nic::cu_count());
 }
 
-// argument checks + dispatch shared by nic_linear_wgrad (one period) and nic_linear_wgrad_periods
-static int wgrad_generic(const float* dY, const float* X, float* slab, int64_t lds_, int32_t N, int32_t K, int32_t n_scenarios,
-                         int32_t ldb, int32_t n_splits, int32_t n_periods, int64_t pstride_dy, int64_t pstride_x, void* stream,
-                         const char* who, int32_t scen_splits = 0, int32_t periods_per_group = 0) {
+// nic_linear_wgrad (one period) and nic_linear_wgrad_periods: argument checks, the plan (wgrad_plan.h), its launches
+static int wgrad_run(nic::WgradEntry entry, const float* dY, const float* X, float* slab, int64_t lds_, int32_t N, int32_t K,
+                     int32_t n_scenarios, int32_t ldb, int32_t n_splits, int32_t n_periods, int64_t pstride_dy, int64_t pstride_x,
+                     void* stream, const char* who) {
     NIC_REQUIRE(dY && X && slab, "%s: null buffer", who);
     NIC_REQUIRE(N > 0 && K > 0 && lds_ >= K + 1, "%s: bad N/K/lds (%d/%d/%lld)", who, N, K, (long long)lds_);
     NIC_REQUIRE(n_splits >= 1, "%s: n_splits must be >= 1", who);
     if (int e = require_ld(who, n_scenarios, ldb)) return e;
-    // (scen_splits > 0: the n_splits slab slots are period groups x scen_splits scenario splits, register-staged kernels only)
-    int chunk = (n_scenarios + (scen_splits > 0 ? scen_splits : n_splits) - 1) / (scen_splits > 0 ? scen_splits : n_splits);
-    chunk = (chunk + BK - 1) / BK * BK;
-    WgParams p{dY, X, slab, lds_, ldb, N, K, n_scenarios, chunk, gemm_variant() == 3 ? 0 : 1, n_periods, pstride_dy, pstride_x, 0,
-               scen_splits, periods_per_group};
-    hipStream_t s = nic::as_stream(stream);
-    int bm, bn;
-    wgrad_tile(N, K, &bm, &bn);
-    const bool dma_ok = ldb % 4 == 0 && n_scenarios % BK == 0 && lds_ % 4 == 0 && (reinterpret_cast<uintptr_t>(dY) & 15) == 0 &&
-                        (reinterpret_cast<uintptr_t>(X) & 15) == 0 && (reinterpret_cast<uintptr_t>(slab) & 15) == 0 &&
-                        (int64_t)N * ldb < (1ll << 28) && (int64_t)K * ldb < (1ll << 28);
-    const bool small_ok = n_periods == 1 && N <= 32 && K <= 128 && ldb % 4 == 0 &&
-                          (reinterpret_cast<uintptr_t>(dY) & 15) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 &&
-                          (int64_t)N * ldb < (1ll << 28) && (int64_t)K * ldb < (1ll << 28);
-    if (small_ok) {  // thin output (<= 32 rows), up to 128 input features: one wave per split, 1..4 accumulators
-        const dim3 g((n_splits + 3) / 4), b(kThreads);
-        nic::note_kernelf("wgrad_small_kernel<%d>", K <= 32 ? 1 : (K <= 64 ? 2 : (K <= 96 ? 3 : 4)));
-        if (K <= 32) hipLaunchKernelGGL(wgrad_small_kernel<1>, g, b, 0, s, p, n_splits);
-        else if (K <= 64) hipLaunchKernelGGL(wgrad_small_kernel<2>, g, b, 0, s, p, n_splits);
-        else if (K <= 96) hipLaunchKernelGGL(wgrad_small_kernel<3>, g, b, 0, s, p, n_splits);
-        else hipLaunchKernelGGL(wgrad_small_kernel<4>, g, b, 0, s, p, n_splits);
+    const nic::WgradOperands operands = nic::wgrad_operands(reinterpret_cast<uintptr_t>(dY) | reinterpret_cast<uintptr_t>(X),
+                                                            reinterpret_cast<uintptr_t>(slab), ldb, lds_, N, K);
+    const nic::WgradPlan plan = nic::wgrad_plan(entry, N, K, n_scenarios, n_periods, n_splits, operands, gemm_variant() == 2);
+    const bool calls = plan.cut == nic::WG_PER_PERIOD;   // nic_linear_wgrad calls: no period strides, launch errors under that name
+    if (!calls && entry == nic::WG_ALL_PERIODS) who = "nic_linear_wgrad_periods";
+    for (nic::WgradLaunch l = nic::wgrad_launch(plan, n_periods, 0); l.n_periods > 0;
+         l = nic::wgrad_launch(plan, n_periods, l.first_period + l.n_periods)) {
+        WgParams p{dY + l.first_period * pstride_dy, X + l.first_period * pstride_x, slab, lds_, ldb, N, K, n_scenarios, plan.chunk,
+                   gemm_variant() == 3 ? 0 : 1, l.n_periods, calls ? 0 : pstride_dy, calls ? 0 : pstride_x, plan.flush_periods,
+                   plan.scen_splits, plan.periods_per_group};
+        kWgLaunch[l.tile](p, plan.slots, operands.buffer, nic::as_stream(stream));
+        if (int e = nic::check_launch(who)) return e;
     }
-    else if (wgrad_dma_shape(N, K) && dma_ok && gemm_variant() != 2 && scen_splits == 0) launch_wg_dma_for(p, n_splits, s);
-    else if (bm == 128 && bn == 128) launch_wg<2, 2, 2, 2>(p, n_splits, s);
-    else if (bm == 128) launch_wg<2, 2, 2, 1>(p, n_splits, s);
-    else if (bm == 64) launch_wg<1, 4, 2, 1>(p, n_splits, s);
-    else launch_wg<1, 4, 1, 2>(p, n_splits, s);
-    return nic::check_launch(who);
+    return 0;
 }
 
 int nic_linear_wgrad(const float* dY, const float* X, float* slab, int64_t lds_, int32_t N, int32_t K, int32_t n_scenarios,
                      int32_t ldb, int32_t n_splits, void* stream) {
-    return wgrad_generic(dY, X, slab, lds_, N, K, n_scenarios, ldb, n_splits, 1, 0, 0, stream, "nic_linear_wgrad");
+    return wgrad_run(nic::WG_ONE_PERIOD, dY, X, slab, lds_, N, K, n_scenarios, ldb, n_splits, 1, 0, 0, stream, "nic_linear_wgrad");
 }
 
 int nic_linear_wgrad_periods(const float* dY, const float* X, float* slab, int64_t lds_, int32_t N, int32_t K,
@@ -1668,54 +1555,10 @@ int nic_linear_wgrad_periods(const float* dY, const float* X, float* slab, int64
     }
     NIC_REQUIRE(period_stride_dy % 4 == 0 && period_stride_x % 4 == 0,
                 "nic_linear_wgrad_periods: period strides must be multiples of 4 elements (16-byte aligned operands)");
-    const bool dma_ok = dY && X && slab && N > 0 && K > 0 && lds_ >= K + 1 && n_splits >= 1 && n_scenarios > 0 && ldb >= n_scenarios &&
-                        wgrad_dma_shape(N, K) && gemm_variant() != 2 && ldb % 4 == 0 && n_scenarios % BK == 0 && lds_ % 4 == 0 &&
-                        (reinterpret_cast<uintptr_t>(dY) & 15) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 &&
-                        (reinterpret_cast<uintptr_t>(slab) & 15) == 0 && (int64_t)N * ldb < (1ll << 28) &&
-                        (int64_t)K * ldb < (1ll << 28);
-    if (!dma_ok) {  // other shapes: the register-staged kernels loop over the periods themselves; tiny layers one launch each
-        const bool small = N <= 32 && K <= 32;
-        if (small || n_periods == 1) {
-            for (int t = 0; t < n_periods; ++t)
-                if (int e = nic_linear_wgrad(dY + t * period_stride_dy, X + t * period_stride_x, slab, lds_, N, K, n_scenarios,
-                                             ldb, n_splits, stream))
-                    return e;
-            return 0;
-        }
-        // register-staged kernels.  With enough slab slots: ONE launch, slot = (period group, scenario split), as long as no
-        // accumulator sums more than ~8k terms (chunk x periods per group)
-        {
-            int ss, g;
-            wgrad_period_factors(n_splits, n_scenarios, n_periods, &ss, &g);
-            int chunk_s = (n_scenarios + ss - 1) / ss;
-            chunk_s = (chunk_s + BK - 1) / BK * BK;
-            const int ppg = (n_periods + g - 1) / g;
-            if (g > 1 && (int64_t)chunk_s * ppg <= 8192)
-                return wgrad_generic(dY, X, slab, lds_, N, K, n_scenarios, ldb, ss * g, n_periods, period_stride_dy, period_stride_x,
-                                     stream, "nic_linear_wgrad_periods", ss, ppg);
-        }
-        // otherwise: a launch per group of periods, so that no accumulator sums more than ~8k terms
-        // before it is added to the slab (see WgParams::flush_periods)
-        int chunk_g = (n_scenarios + n_splits - 1) / n_splits;
-        const int group = 8192 / (chunk_g > 0 ? chunk_g : 1) > 0 ? 8192 / (chunk_g > 0 ? chunk_g : 1) : 1;
-        for (int t = 0; t < n_periods; t += group) {
-            const int n = n_periods - t < group ? n_periods - t : group;
-            if (int e = wgrad_generic(dY + t * period_stride_dy, X + t * period_stride_x, slab, lds_, N, K, n_scenarios, ldb,
-                                      n_splits, n, period_stride_dy, period_stride_x, stream, "nic_linear_wgrad_periods"))
-                return e;
-        }
-        return 0;
-    }
-    int scen_splits, groups;
-    wgrad_period_factors(n_splits, n_scenarios, n_periods, &scen_splits, &groups);
-    int chunk = (n_scenarios + scen_splits - 1) / scen_splits;
-    chunk = (chunk + BK - 1) / BK * BK;
-    const int flush = 8192 / chunk > 0 ? 8192 / chunk : 1;
-    const int ppg = (n_periods + groups - 1) / groups;
-    WgParams p{dY, X, slab, lds_, ldb, N, K, n_scenarios, chunk, gemm_variant() == 3 ? 0 : 1, n_periods, period_stride_dy,
-               period_stride_x, flush, scen_splits, ppg};
-    launch_wg_dma_for(p, scen_splits * groups, nic::as_stream(stream));
-    return nic::check_launch("nic_linear_wgrad_periods");
+    // (a horizon of one period and the tiny layers ran as nic_linear_wgrad calls: argument errors come under that name)
+    const char* who = n_periods == 1 || (N <= 32 && K <= 32) ? "nic_linear_wgrad" : "nic_linear_wgrad_periods";
+    return wgrad_run(nic::WG_ALL_PERIODS, dY, X, slab, lds_, N, K, n_scenarios, ldb, n_splits, n_periods, period_stride_dy,
+                     period_stride_x, stream, who);
 }
 
 // many splits, few outputs (the small layers): one wavefront per output element, lanes stride over the splits

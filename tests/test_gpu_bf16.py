@@ -303,7 +303,8 @@ def test_sweep_wgrad(N, K):
 
 
 def _period_factors(n_slots, n, T):
-    """`period_factors` and `wgrad_bf16` of csrc/linear_bf16.hip restated: (scenario splits, period groups, chunk, periods per
+    """`period_factors` / `wgrad_flush_periods` of csrc/wgrad_plan.h (what `wgrad_bf16` of csrc/linear_bf16.hip launches with)
+    restated: (scenario splits, period groups, chunk, periods per
     group, flush).  It CHOOSES the cases below and names the slots a launch owns; no numerical result is judged by it."""
     ss = max(1, min(n_slots, max(1, n // 128)))
     groups = max(1, min(n_slots // ss, T))

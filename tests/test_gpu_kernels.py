@@ -3,6 +3,10 @@
 env step / policy heads: the same checks as the host-sim build (golden vectors + oracle autograd);
 policy GEMMs: against float64 torch on the same inputs (FP32 MFMA = exact f32 products, f32 accumulation);
 sampler: moments + sharding invariance (statistical parity with numpy)."""
+import json
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -11,6 +15,9 @@ import kernel_checks as kc
 from golden_io import case_names
 from neural_inventory_control_amd import _lib, ops
 from neural_inventory_control_amd.layout import pad_ld
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import record_wgrad_pins  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -428,6 +435,26 @@ def test_linear_wgrad_periods_splits_the_horizon_into_period_groups(N, K, B, T, 
     _close(db, want_b, torch.full((N,), 1.0 * T * B), "bgrad period groups")
     used = int((slab.abs().sum(dim=(1, 2)) > 0).sum())
     assert 1 <= used <= n_slots
+
+
+def _wgrad_pins():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wgrad_dispatch_pins.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("case", record_wgrad_pins.PIN_CASES, ids=[c[0] for c in record_wgrad_pins.PIN_CASES])
+def test_wgrad_dispatch_is_pinned_to_the_parent(case):
+    """The weight-gradient dispatch does what it did before the launch plan moved into csrc/wgrad_plan.h: for the smallest shapes
+    that reach each branch (tools/record_wgrad_pins.py, recorded there on an MI355X at the commit before) the same kernel, the same
+    number of slab slots written, and bit-identical dW and db (the kernels use no atomics; a case whose bits differed between two
+    recordings has "sha256": null and is pinned by kernel and slots only)."""
+    want = _wgrad_pins()[case[0]]
+    got = record_wgrad_pins.run_pin_case(case)
+    print(f"PIN {case[0]}: {got} (recorded: {want})")
+    assert got["kernel"] == want["kernel"]
+    assert got["used_slots"] == want["used_slots"]
+    if want["sha256"] is not None:
+        assert got["sha256"] == want["sha256"]
 
 
 def test_every_wx_tile_of_the_picker_is_exercised_and_correct():
