@@ -11,10 +11,11 @@ import numpy as np
 import pytest
 import torch
 
+import env_exact_cases as ex
 import kernel_checks as kc
 from golden_io import case_names
 from neural_inventory_control_amd import _lib, ops
-from neural_inventory_control_amd.layout import pad_ld
+from neural_inventory_control_amd.layout import pad_ld, to_soa
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import record_wgrad_pins  # noqa: E402
@@ -47,6 +48,17 @@ def test_env_backward_matches_oracle_autograd(be, name, profit):
 @pytest.mark.parametrize("trans", [False, True])
 def test_warehouse_head(be, S, Wn, adj, trans):
     kc.check_warehouse_head(be, S, Wn, adj, trans)
+
+
+@pytest.mark.parametrize("S,Wn,adj", kc.WAREHOUSE_HEAD_REFEREE_CASES, ids=[f"S{c[0]}-Wn{c[1]}" for c in kc.WAREHOUSE_HEAD_REFEREE_CASES])
+@pytest.mark.parametrize("trans", [False, True])
+def test_warehouse_head_against_the_fp64_referee(be, S, Wn, adj, trans):
+    """The dispatch points of nic_head_warehouse_* beyond WAREHOUSE_HEAD_CASES - workgroups striding over more than 8 (quad) or 4
+    (one-lane) warehouses, the sq = 8 variant, the one-lane kernels for S > 64, three scenario workgroups - judged by the float64
+    expression (kc.HEAD_REFEREE_C: the device's v_exp_f32 / v_rcp_f32 softmax has its own measured ratios)."""
+    kc.check_warehouse_head(be, S, Wn, adj, trans, B=kc.WAREHOUSE_HEAD_REFEREE_B, referee=True)
+    want = "head_warehouse_bwd_kernel" if S > 64 else f"head_warehouse_bwd_quad_kernel<{4 if S <= 16 else (8 if S <= 32 else 16)}>"
+    assert be.l.nic_last_kernel().decode() == want
 
 
 def test_softplus_head(be):
@@ -132,6 +144,136 @@ def test_env_step_zero_lead_rule_inside_the_launch_equals_the_torch_patch(B, S, 
     want_g[:, :, :B] += (gt.unsqueeze(2) * hit).permute(1, 2, 0)
     assert torch.equal(gres[True][2], want_g)
     assert all(torch.equal(gres[True][i], gres[False][i]) for i in (0, 1, 3))
+
+
+# ---- one period on exact inputs: bit-equal to the oracle at every shape the C ABI admits (tests/env_exact_cases.py) -------------
+@pytest.mark.parametrize("case", ex.ENV_EXACT_CASES, ids=ex.ENV_EXACT_IDS)
+def test_env_step_equals_the_oracle_bit_for_bit(be, case):
+    """nic_env_step_fwd / _bwd on dyadic inputs with planted ties: next state, reward, the three state gradients and the three
+    order gradients `torch.equal` to the oracle (float32 == float64 there), padding columns untouched, and the launched
+    instantiation asserted by name.  What this adds to the host tier: the LDS exchange in rounds of 8 warehouses (cw[] / gwa[]
+    above index 7, the lane walk inside a later round), several and ragged workgroups, the <4>, <8> and <16> instantiations."""
+    ex.check_env_exact(be, case, in_place=case.in_place, null_grads=case.null_grads)
+
+
+def test_env_exact_table_launches_every_instantiation():
+    assert {ex.expected_variant(c) for c in ex.ENV_EXACT_CASES} == {4, 8, 16}   # (each case asserts its own by name)
+
+
+# ---- fused head + env step against the two launches -------------------------------------------------------------------------
+def _head_env_variant(S, Ws, Ww):
+    m = max(Ws, Ww)
+    return (4 if m <= 4 else (8 if m <= 8 else _lib.NIC_MAX_SLOTS)), (4 if S <= 16 else 16)
+
+
+#                 S  Wn   B  Ws  Ww trans compact
+HEAD_ENV_CASES = [(5, 1, 65, 3, 3, False, False),      # <4,4>
+                  (16, 4, 130, 7, 4, True, False),     # <8,4>
+                  (5, 9, 65, 4, 12, False, False),     # <16,4>, second chunk round
+                  (17, 9, 130, 3, 2, True, True),      # <4,16>, compact logits
+                  (64, 4, 65, 5, 7, False, False),     # <8,16>
+                  (17, 32, 65, 12, 3, True, False),    # <16,16>, four chunk rounds
+                  (64, 32, 130, 3, 3, False, False),   # <4,16>, the largest admitted setting
+                  (16, 32, 65, 2, 8, True, False),     # <8,4>
+                  (17, 9, 65, 12, 12, False, True),    # <16,16>, compact logits
+                  (5, 4, 130, 3, 3, True, False),      # <4,4>
+                  (64, 1, 130, 12, 3, True, False),    # <16,16>
+                  (16, 9, 130, 3, 16, False, False)]   # <16,4>
+
+
+def test_head_env_table_launches_every_instantiation():
+    assert {_head_env_variant(c[0], c[3], c[4]) for c in HEAD_ENV_CASES} == {(w, q) for w in (4, 8, 16) for q in (4, 16)}
+    assert {c[1] for c in HEAD_ENV_CASES} == {1, 4, 9, 32} and {c[2] for c in HEAD_ENV_CASES} == {65, 130}
+    assert any(c[6] and c[0] == 17 and c[1] == 9 for c in HEAD_ENV_CASES)
+
+
+@pytest.mark.parametrize("S,Wn,B,Ws,Ww,trans,compact", HEAD_ENV_CASES)
+def test_head_env_fused_equals_the_two_launches(be, S, Wn, B, Ws, Ww, trans, compact):
+    """nic_head_env_fwd against nic_head_warehouse_fwd + nic_env_step_fwd, and nic_head_env_bwd against nic_env_step_bwd +
+    nic_head_warehouse_bwd, on identical inputs (random float32 logits): the orders written into io.store_orders / io.wh_orders, next
+    state, reward, g_store_in, g_wh_in, dZ and the order-gradient scratch `torch.equal` (csrc/head_env.hip promises bit identity).
+    All six <MAXW, MAXSQ> instantiations, 1 / 4 / 9 / 32 warehouses, two and three scenario workgroups with a ragged last one, an
+    adjacency with an empty and a one-store warehouse, and the compact-logits addressing (logit_rows / first_wh_row built the way
+    FusedRollout builds them).  The two separate launches are tied to independent references by the exact-input sweep above and
+    the warehouse-head tests; this carries that over to the fused launch."""
+    from neural_inventory_control_amd.layout import EnvProblem, Table
+    from neural_inventory_control_amd.ops import EnvState
+    DEV = "cuda"
+    g = torch.Generator().manual_seed(7 * S + 131 * Wn + B + Ws + 3 * Ww + int(trans))
+    adj = (torch.rand(Wn, S, generator=g) < 0.5).int()
+    adj[0] = 1
+    if Wn == 1 and S > 1:
+        adj[0, S - 1] = 0
+    if Wn > 1:
+        adj[1] = 0
+        adj[1, S // 2] = 1      # a one-store warehouse
+    if Wn > 2:
+        adj[2] = 0              # an empty warehouse
+    lead1 = torch.randint(1, Ws + 1, (S, Wn), generator=g).float() * adj.t()    # no edge: lead time 0 (and an exactly-zero order)
+    problem = {"n_stores": S, "n_warehouses": Wn, "n_extra_echelons": 0, "lost_demand": True, "maximize_profit": False,
+               "warehouse_store_adjacency": adj.tolist()}
+    data = {"demands": torch.rand(B, S, 1, generator=g) * 5, "initial_inventories": torch.rand(B, S, Ws, generator=g) * 4,
+            "underage_costs": 5 + torch.rand(B, S, generator=g) * 4, "holding_costs": torch.rand(B, S, generator=g),
+            "lead_times": lead1.unsqueeze(0).expand(B, S, Wn),
+            "initial_warehouse_inventories": torch.rand(B, Wn, Ww, generator=g) * 2 * S,
+            "warehouse_holding_costs": torch.rand(B, Wn, generator=g), "warehouse_lead_times": torch.randint(1, Ww + 1, (Wn,), generator=g).float().expand(B, Wn),
+            "warehouse_edge_costs": torch.rand(B, Wn, generator=g)}
+    prob = EnvProblem(problem, data, DEV)
+    ld = prob.ldb
+    st = EnvState(to_soa(data["initial_inventories"].to(DEV), ld), to_soa(data["initial_warehouse_inventories"].to(DEV), ld), None)
+    dem = Table(to_soa(data["demands"][:, :, 0].to(DEV), ld), ld, 1)
+    adj_i = adj.contiguous().to(DEV)
+    ub = 40.0
+    n_rows = S * Wn + Wn
+    Z = torch.zeros(n_rows, ld, device=DEV)
+    Z[:, :B] = (torch.randn(n_rows, B, generator=g) * 2).to(DEV)
+    rows_kw, Zf, live_rows = {}, Z, None
+    if compact:   # rollout.py: the logits layer computes the connected pairs and the warehouses' own rows only
+        conn = adj.tolist()
+        live = [s_ * Wn + w for s_ in range(S) for w in range(Wn) if conn[w][s_]] + [S * Wn + w for w in range(Wn)]
+        pos = {r: i for i, r in enumerate(live)}
+        zrow = torch.tensor([[pos.get(s_ * Wn + w, 0) for s_ in range(S)] for w in range(Wn)], dtype=torch.int32, device=DEV)
+        live_rows = torch.tensor(live, dtype=torch.long, device=DEV)
+        assert len(live) < n_rows
+        Zf = Z[live_rows].contiguous()
+        rows_kw = dict(logit_rows=zrow, first_wh_row=len(live) - Wn)
+    g_next = EnvState(to_soa(torch.randn(B, S, Ws, generator=g).to(DEV), ld), to_soa(torch.randn(B, Wn, Ww, generator=g).to(DEV), ld), None)
+    g_reward = torch.zeros(ld, device=DEV)
+    g_reward[:B] = torch.randn(B, generator=g).to(DEV)
+    z = lambda *shape: torch.zeros(*shape, device=DEV)   # noqa: E731
+    mw, sq = _head_env_variant(S, Ws, Ww)
+
+    # the two launches
+    so_a, wo_a = z(S, Wn, ld), z(Wn, ld)
+    ops.head_warehouse_fwd(Z, st.wh, adj_i, ub, trans, so_a, wo_a, S, Wn, Ww, B)
+    ts_a, tw_a = Table(so_a, Wn * ld, 1, ld), Table(wo_a, ld, 1)
+    out_a, r_a = ops.env_step_fwd(prob, st, dem, ts_a, tw_a, None)
+    gin_a, gord_a = ops.env_step_bwd(prob, st, dem, ts_a, tw_a, None, g_next, Table(g_reward, 0, 1))
+    dZ_a = z(n_rows, ld)
+    ops.head_warehouse_bwd(Z, st.wh, adj_i, ub, trans, gord_a[0], gord_a[1], dZ_a, gin_a.wh, S, Wn, Ww, B)
+
+    # the fused launches
+    so_b, wo_b = z(S, Wn, ld), z(Wn, ld)
+    ts_b, tw_b = Table(so_b, Wn * ld, 1, ld), Table(wo_b, ld, 1)
+    out_b, r_b = ops.head_env_fwd(prob, st, dem, ts_b, tw_b, Zf, adj_i, ub, trans, EnvState.zeros_like(prob), z(ld), **rows_kw)
+    assert be.l.nic_last_kernel().decode() == f"head_env_fwd_kernel<{mw},{sq}>"
+    gin_b, gord_b, dZ_b = EnvState.zeros_like(prob), (z(S, Wn, ld), z(Wn, ld)), z(Zf.shape[0], ld)
+    ops.head_env_bwd(prob, st, dem, ts_b, tw_b, Zf, adj_i, ub, trans, g_next, Table(g_reward, 0, 1), gin_b, gord_b, dZ_b, **rows_kw)
+    assert be.l.nic_last_kernel().decode() == f"head_env_bwd_kernel<{mw},{sq}>"
+    torch.cuda.synchronize()
+
+    assert bool((so_a != 0).any()) and bool((dZ_a != 0).any())
+    assert torch.equal(so_b, so_a) and torch.equal(wo_b, wo_a), "orders"
+    assert torch.equal(out_b.store, out_a.store) and torch.equal(out_b.wh, out_a.wh), "next state"
+    assert torch.equal(r_b, r_a), "reward"
+    assert torch.equal(gin_b.store, gin_a.store), "g_store_in"
+    assert torch.equal(gin_b.wh, gin_a.wh), "g_wh_in"
+    assert torch.equal(gord_b[0], gord_a[0]) and torch.equal(gord_b[1], gord_a[1]), "order-gradient scratch"
+    assert torch.equal(dZ_b, dZ_a[live_rows] if compact else dZ_a), "dZ"
+    if compact:   # the rows without an edge carry no gradient
+        dead = torch.ones(n_rows, dtype=torch.bool, device=DEV)
+        dead[live_rows] = False
+        assert not bool(dZ_a[dead].any())
 
 
 def test_env_rejects_bad_arguments(be):

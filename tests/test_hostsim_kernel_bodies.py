@@ -29,6 +29,13 @@ def test_warehouse_head(be, S, Wn, adj, trans):
     kc.check_warehouse_head(be, S, Wn, adj, trans)
 
 
+@pytest.mark.parametrize("S,Wn,adj", kc.WAREHOUSE_HEAD_REFEREE_CASES, ids=[f"S{c[0]}-Wn{c[1]}" for c in kc.WAREHOUSE_HEAD_REFEREE_CASES])
+@pytest.mark.parametrize("trans", [False, True])
+def test_warehouse_head_against_the_fp64_referee(be, S, Wn, adj, trans):
+    """more than 8 warehouses, 17..32 and more than 64 stores, one store: judged by the float64 expression (kc.HEAD_REFEREE_C)"""
+    kc.check_warehouse_head(be, S, Wn, adj, trans, B=kc.WAREHOUSE_HEAD_REFEREE_B, referee=True)
+
+
 def test_softplus_head(be):
     kc.check_softplus_head(be)
 
