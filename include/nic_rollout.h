@@ -380,6 +380,48 @@ int nic_small_rollout_reduce_scratch(int32_t n_rows, int32_t P, int64_t n_reward
 int nic_small_rollout_reduce(const float* slab, int32_t n_rows, int64_t slab_stride, int32_t P, float* grad, const float* rewards,
                              int64_t n_reward_elems, int64_t ignore_elems, float* totals, float* scratch, void* stream);
 
+/* ---- K small policies of ONE architecture on ONE batch: a forward launch, a backward launch and a reduction for all of them ----
+ * Model m (grid y) runs the instruction stream of the single-model kernels above on its own slice of every per-model buffer:
+ * the slice has exactly the single-model layout (the wave-native history order of lane_scenarios = 16 included) and starts at
+ * m * stride elements; the demand trace, the initial state, the cost / lead-time tables and g_reward are shared.  Every model's
+ * numbers are the bits of a single-model call on its slice.  `NicSmallRolloutDesc::weights` points at model 0.
+ * Strides are in floats; csrc/small_ensemble_plan.h gives the slice sizes (nic_small_rollout_ensemble_slices) and the checks: 1 <=
+ * n_models <= 65535, every stride of a buffer that is passed >= its slice, the strides of the rewards and the three histories
+ * multiples of 4 (16-byte accesses), slab_row_stride >= the packed-weight count.  A refused request returns non-zero, leaves a
+ * message in nic_last_error and launches nothing. */
+typedef struct NicSmallEnsemble {
+    int32_t n_models, reserved;
+    int64_t weights, rewards, final_state; /* packed weights [K][>= P]; rewards [K][>= T*ldb]; final state [K][>= F*ldb] */
+    int64_t states, hidden, logits;        /* the three histories (ignored where the pointer is NULL) */
+    int64_t slab;                          /* partial gradients [K][>= rows * slab_row_stride] */
+    int64_t grad, scratch;                 /* reduction: grad [K][>= P], scratch [K][>= nic_small_rollout_reduce_scratch(...)] */
+} NicSmallEnsemble;
+/* floats of ONE model's slice of every buffer for a descriptor (its lane_scenarios decides the history rows: 16, else 32) */
+typedef struct NicSmallEnsembleSlices {
+    int64_t weights;                       /* packed-weight count P0 */
+    int64_t rewards, final_state;          /* T * ldb, F * ldb */
+    int64_t states, hidden, logits;        /* rows * T * ldb: NIC_SR16_STATE_ROWS(F) / 32 * n_hidden / NIC_SR16_LOGIT_ROWS(n_out) with 16
+                                              scenarios per wavefront, F / 32 * n_hidden / n_out with 32 */
+    int64_t slab_rows, slab_row_stride;    /* one partial gradient per wavefront; P0 rounded up to 4 (the least is P0) */
+    int64_t slab, grad;                    /* slab_rows * slab_row_stride; slab_row_stride */
+    int64_t scratch;                       /* nic_small_rollout_reduce_scratch(slab_rows, slab_row_stride, T * ldb) */
+} NicSmallEnsembleSlices;
+int nic_small_rollout_ensemble_slices(const NicSmallRolloutDesc* d, NicSmallEnsembleSlices* out);
+/* K forward rollouts (trainer.py:181-216, `simulate_batch`, once per model) in one launch.  rewards [K][T][ldb], state_final
+ * [K][F][ldb]; the histories may be NULL (evaluation). */
+int nic_small_rollout_ensemble_fwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, float* rewards, float* state_final,
+                                   float* states_hist, float* hidden_hist, float* logits_hist, void* stream);
+/* K backward sweeps with in-kernel weight gradients (trainer.py:181-216 under `backward`, trainer.py:173, once per model) in one
+ * launch: model m's wavefront w stores its partial gradient to slab[m * e->slab + w * slab_row_stride ...]. */
+int nic_small_rollout_ensemble_bwd_wgrad(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const float* states_hist,
+                                         const float* hidden_hist, const float* logits_hist, NicTable2 g_reward, float* slab,
+                                         int64_t slab_row_stride, void* stream);
+/* nic_small_rollout_reduce for all K models in its two launches (trainer.py:169-173 and :207-210, once per model): grad [K][e->grad],
+ * totals [K][2].  Either pair (slab, grad) / (rewards, totals) may be NULL. */
+int nic_small_rollout_ensemble_reduce(const NicSmallEnsemble* e, const float* slab, int32_t n_rows, int64_t slab_row_stride, int32_t P,
+                                      float* grad, const float* rewards, int64_t n_reward_elems, int64_t ignore_elems, float* totals,
+                                      float* scratch, void* stream);
+
 /* ---- whole-horizon rollout of the closed-form policies ---------------------------------------------------------
  * base_stock (neural_networks.py:216-229), capped_base_stock (:296-311) and echelon_stock (:231-294) for T periods of
  * Trainer.simulate_batch (trainer.py:190-213) in ONE launch, forward AND gradient: one lane per store chain, pipelines in

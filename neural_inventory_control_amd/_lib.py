@@ -73,6 +73,17 @@ class NicSmallRolloutDesc(C.Structure):
                                             "ech_holding", "ech_lead")])
 
 
+class NicSmallEnsemble(C.Structure):
+    """K models in one launch: floats between two models' slices of every per-model buffer (include/nic_rollout.h)"""
+    _fields_ = ([("n_models", C.c_int32), ("reserved", C.c_int32)]
+                + [(n, C.c_int64) for n in ("weights", "rewards", "final_state", "states", "hidden", "logits", "slab", "grad", "scratch")])
+
+
+class NicSmallEnsembleSlices(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("weights", "rewards", "final_state", "states", "hidden", "logits", "slab_rows",
+                                         "slab_row_stride", "slab", "grad", "scratch")]
+
+
 class NicHorizonDesc(C.Structure):
     _fields_ = ([("io", NicEnvStepIO)] + [(n, C.c_int32) for n in ("T", "t0", "H1", "H2", "n_out", "round_orders")]
                 + [("W1", C.c_void_p), ("ldw1", C.c_int64), ("W2", C.c_void_p), ("ldw2", C.c_int64), ("W3", C.c_void_p),
@@ -195,6 +206,11 @@ PROTOTYPES = {
     "nic_small_rollout_bwd_wgrad": (C.c_int, [C.POINTER(NicSmallRolloutDesc), _vp, _vp, _vp, NicTable2, _vp, _i64, _vp]),
     "nic_small_rollout_reduce_scratch": (C.c_int, [C.c_int32, C.c_int32, _i64]),
     "nic_small_rollout_reduce": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "nic_small_rollout_ensemble_slices": (C.c_int, [C.POINTER(NicSmallRolloutDesc), C.POINTER(NicSmallEnsembleSlices)]),
+    "nic_small_rollout_ensemble_fwd": (C.c_int, [C.POINTER(NicSmallRolloutDesc), C.POINTER(NicSmallEnsemble), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nic_small_rollout_ensemble_bwd_wgrad": (C.c_int, [C.POINTER(NicSmallRolloutDesc), C.POINTER(NicSmallEnsemble), _vp, _vp, _vp, NicTable2,
+                                                       _vp, _i64, _vp]),
+    "nic_small_rollout_ensemble_reduce": (C.c_int, [C.POINTER(NicSmallEnsemble), _vp, _i32, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "nic_horizon_rollout_ok": (C.c_int, [C.POINTER(NicHorizonDesc)]),
     "nic_horizon_rollout_fwd": (C.c_int, [C.POINTER(NicHorizonDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nic_horizon_rollout_bwd": (C.c_int, [C.POINTER(NicHorizonDesc), _vp, _vp, _vp, _vp, _vp, NicTable2, _vp, _vp, _vp, _vp]),

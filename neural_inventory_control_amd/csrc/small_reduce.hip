@@ -5,26 +5,17 @@
 // workgroup per 64 columns (and one for the rewards) adds the partial sums in a fixed order.  No atomics, no semaphore pass:
 // the result depends on the shapes only (bit-reproducible from call to call).  Replaces trainer.py:169-173's `sum` of the costs
 // and autograd's accumulation of the weight gradients for these policies (csrc/small_rollout16.hip).
+// K models (nic_small_rollout_ensemble_reduce): grid y = model, every buffer of model m starts m x its stride (MStrides) from the
+// base, totals at 2 m; the single-model entry point launches one grid row with zero strides.  The plan (chunks, row groups, cost
+// blocks) is csrc/small_ensemble_plan.h's sr_reduce_plan, the same for every model.
 #include "nic_common.h"
+#include "small_ensemble_plan.h"
 
 namespace {
-constexpr int kT = 256;        // threads per workgroup = columns per chunk
-constexpr int kMaxGroups = 64;  // row groups of the slab
-constexpr int kRewardBlocks = 256;
-
-struct Plan {
-    int cc, rg, rows_per_group, nb;
-};
-Plan plan_for(int n_rows, int P, int64_t n_reward_elems) {
-    Plan p;
-    p.cc = P > 0 && n_rows > 0 ? (P + kT - 1) / kT : 0;
-    p.rg = p.cc ? (n_rows < kMaxGroups ? n_rows : kMaxGroups) : 0;
-    p.rows_per_group = p.rg ? (n_rows + p.rg - 1) / p.rg : 0;
-    if (p.rg) p.rg = (n_rows + p.rows_per_group - 1) / p.rows_per_group;   // (no empty groups)
-    const int64_t n4 = n_reward_elems / 4;
-    p.nb = n4 > 0 ? (int)((n4 + kT - 1) / kT < kRewardBlocks ? (n4 + kT - 1) / kT : kRewardBlocks) : 0;
-    return p;
-}
+constexpr int kT = nic::kSrReduceThreads;        // threads per workgroup = columns per chunk
+using Plan = nic::SrReducePlan;
+Plan plan_for(int n_rows, int P, int64_t n_reward_elems) { return nic::sr_reduce_plan(n_rows, P, n_reward_elems); }
+struct MStrides { int64_t slab, rewards, scratch, grad; };   // floats between two models' slices
 
 __device__ __forceinline__ float block_sum(float v, float* lds) {
     lds[threadIdx.x] = v;
@@ -41,8 +32,14 @@ __device__ __forceinline__ float block_sum(float v, float* lds) {
 
 __global__ __launch_bounds__(kT) void sr_reduce_stage1(const float* __restrict__ slab, int n_rows, int64_t stride, int P, int cc, int rg,
                                                        int rows_per_group, const float* __restrict__ rewards, int64_t n4,
-                                                       int64_t ignore4, int nb, float* __restrict__ scratch) {
+                                                       int64_t ignore4, int nb, float* __restrict__ scratch, MStrides ms) {
     __shared__ float lds[kT];
+    {
+        const int64_t m = blockIdx.y;
+        if (slab) slab += m * ms.slab;
+        if (rewards) rewards += m * ms.rewards;
+        scratch += m * ms.scratch;
+    }
     const int bid = blockIdx.x, tid = threadIdx.x;
     if (bid < cc * rg) {
         const int c = bid % cc, r = bid / cc, col = c * kT + tid;
@@ -90,8 +87,14 @@ __global__ __launch_bounds__(kT) void sr_reduce_stage1(const float* __restrict__
 // Stage 2: workgroup b < ceil(P / 64) owns 64 columns; its four wavefronts each add every fourth row group (independent loads in
 // flight), wavefront 0 adds the four partial sums in order.  The last workgroup adds the cost partials.
 __global__ __launch_bounds__(kT) void sr_reduce_stage2(const float* __restrict__ scratch, int P, int cc, int rg, int nb, int col_blocks,
-                                                       float* __restrict__ grad, float* __restrict__ totals) {
+                                                       float* __restrict__ grad, float* __restrict__ totals, MStrides ms) {
     __shared__ float lds[kT];
+    {
+        const int64_t m = blockIdx.y;
+        scratch += m * ms.scratch;
+        if (grad) grad += m * ms.grad;
+        if (totals) totals += 2 * m;
+    }
     const int bid = blockIdx.x, tid = threadIdx.x;
     if (bid < col_blocks) {
         const int lane = tid & 63, w = tid >> 6, col = bid * 64 + lane;
@@ -122,36 +125,64 @@ __global__ __launch_bounds__(kT) void sr_reduce_stage2(const float* __restrict__
         totals[1] = r_all;
     }
 }
+int launch_reduce(const float* slab, int32_t n_rows, int64_t slab_stride, int32_t P, float* grad, const float* rewards,
+                  int64_t n_reward_elems, int64_t ignore_elems, float* totals, float* scratch, int n_models, MStrides ms, void* stream,
+                  const char* who) {
+    const Plan p = plan_for(slab ? n_rows : 0, slab ? P : 0, rewards ? n_reward_elems : 0);
+    hipStream_t s = nic::as_stream(stream);
+    if (n_models > 0) nic::note_kernelf("sr_reduce_stage1+2<%d,%d,%d,models=%d>", p.cc, p.rg, p.nb, n_models);
+    else nic::note_kernelf("sr_reduce_stage1+2<%d,%d,%d>", p.cc, p.rg, p.nb);
+    const unsigned gy = n_models > 0 ? n_models : 1;
+    hipLaunchKernelGGL(sr_reduce_stage1, dim3(p.cc * p.rg + p.nb, gy), dim3(kT), 0, s, slab, n_rows, slab_stride, P, p.cc, p.rg,
+                       p.rows_per_group, rewards, n_reward_elems / 4, ignore_elems / 4, p.nb, scratch, ms);
+    const int col_blocks = p.cc ? (P + 63) / 64 : 0;
+    hipLaunchKernelGGL(sr_reduce_stage2, dim3(col_blocks + (p.nb ? 1 : 0), gy), dim3(kT), 0, s, scratch, P, p.cc, p.rg, p.nb, col_blocks,
+                       grad, totals, ms);
+    return nic::check_launch(who);
+}
+
+// the argument checks both entry points share
+int check_args(const char* who, const float* slab, int32_t n_rows, int64_t slab_stride, int32_t P, const float* grad, const float* rewards,
+               int64_t n_reward_elems, int64_t ignore_elems, const float* totals, const float* scratch) {
+    NIC_REQUIRE(scratch, "%s: null scratch buffer", who);
+    NIC_REQUIRE((slab == nullptr) == (grad == nullptr) && (rewards == nullptr) == (totals == nullptr),
+                "%s: slab / grad and rewards / totals go together", who);
+    NIC_REQUIRE(slab || rewards, "%s: nothing to reduce", who);
+    NIC_REQUIRE(!slab || (n_rows > 0 && P > 0 && slab_stride >= P), "%s: bad slab shape (%d rows, %d columns, stride %lld)", who,
+                n_rows, P, (long long)slab_stride);
+    NIC_REQUIRE(!rewards || (n_reward_elems > 0 && n_reward_elems % 4 == 0 && ignore_elems >= 0 && ignore_elems % 4 == 0 &&
+                             (reinterpret_cast<uintptr_t>(rewards) & 15) == 0),
+                "%s: the costs must be 16-byte aligned and a multiple of 4 floats long (%lld, first reported %lld)", who,
+                (long long)n_reward_elems, (long long)ignore_elems);
+    return 0;
+}
 }  // namespace
 
 extern "C" {
 
 int nic_small_rollout_reduce_scratch(int32_t n_rows, int32_t P, int64_t n_reward_elems) {
-    const Plan p = plan_for(n_rows, P, n_reward_elems);
-    return p.cc * p.rg * kT + 2 * p.nb + 4;   // (<= 64 row groups x the column chunks x 256 floats)
+    return nic::sr_reduce_scratch(n_rows, P, n_reward_elems);
 }
 
 int nic_small_rollout_reduce(const float* slab, int32_t n_rows, int64_t slab_stride, int32_t P, float* grad, const float* rewards,
                              int64_t n_reward_elems, int64_t ignore_elems, float* totals, float* scratch, void* stream) {
-    NIC_REQUIRE(scratch, "nic_small_rollout_reduce: null scratch buffer");
-    NIC_REQUIRE((slab == nullptr) == (grad == nullptr) && (rewards == nullptr) == (totals == nullptr),
-                "nic_small_rollout_reduce: slab / grad and rewards / totals go together");
-    NIC_REQUIRE(slab || rewards, "nic_small_rollout_reduce: nothing to reduce");
-    NIC_REQUIRE(!slab || (n_rows > 0 && P > 0 && slab_stride >= P), "nic_small_rollout_reduce: bad slab shape (%d rows, %d columns, stride %lld)",
-                n_rows, P, (long long)slab_stride);
-    NIC_REQUIRE(!rewards || (n_reward_elems > 0 && n_reward_elems % 4 == 0 && ignore_elems >= 0 && ignore_elems % 4 == 0 &&
-                             (reinterpret_cast<uintptr_t>(rewards) & 15) == 0),
-                "nic_small_rollout_reduce: the costs must be 16-byte aligned and a multiple of 4 floats long (%lld, first reported %lld)",
-                (long long)n_reward_elems, (long long)ignore_elems);
-    const Plan p = plan_for(slab ? n_rows : 0, slab ? P : 0, rewards ? n_reward_elems : 0);
-    hipStream_t s = nic::as_stream(stream);
-    nic::note_kernelf("sr_reduce_stage1+2<%d,%d,%d>", p.cc, p.rg, p.nb);
-    hipLaunchKernelGGL(sr_reduce_stage1, dim3(p.cc * p.rg + p.nb), dim3(kT), 0, s, slab, n_rows, slab_stride, P, p.cc, p.rg,
-                       p.rows_per_group, rewards, n_reward_elems / 4, ignore_elems / 4, p.nb, scratch);
-    const int col_blocks = p.cc ? (P + 63) / 64 : 0;
-    hipLaunchKernelGGL(sr_reduce_stage2, dim3(col_blocks + (p.nb ? 1 : 0)), dim3(kT), 0, s, scratch, P, p.cc, p.rg, p.nb, col_blocks, grad,
-                       totals);
-    return nic::check_launch("nic_small_rollout_reduce");
+    if (int r = check_args("nic_small_rollout_reduce", slab, n_rows, slab_stride, P, grad, rewards, n_reward_elems, ignore_elems, totals, scratch))
+        return r;
+    return launch_reduce(slab, n_rows, slab_stride, P, grad, rewards, n_reward_elems, ignore_elems, totals, scratch, 0, MStrides{0, 0, 0, 0},
+                         stream, "nic_small_rollout_reduce");
+}
+
+int nic_small_rollout_ensemble_reduce(const NicSmallEnsemble* e, const float* slab, int32_t n_rows, int64_t slab_row_stride, int32_t P,
+                                      float* grad, const float* rewards, int64_t n_reward_elems, int64_t ignore_elems, float* totals,
+                                      float* scratch, void* stream) {
+    NIC_REQUIRE(e != nullptr, "nic_small_rollout_ensemble_reduce: null ensemble");
+    if (int r = check_args("nic_small_rollout_ensemble_reduce", slab, n_rows, slab_row_stride, P, grad, rewards, n_reward_elems, ignore_elems,
+                           totals, scratch))
+        return r;
+    const int why = nic::small_ensemble_check_reduce(*e, slab != nullptr, n_rows, slab_row_stride, P, rewards != nullptr, n_reward_elems);
+    NIC_REQUIRE(why == 0, "nic_small_rollout_ensemble_reduce: %s (%d models)", nic::small_ensemble_reason(why), e->n_models);
+    return launch_reduce(slab, n_rows, slab_row_stride, P, grad, rewards, n_reward_elems, ignore_elems, totals, scratch, e->n_models,
+                         MStrides{e->slab, e->rewards, e->scratch, e->grad}, stream, "nic_small_rollout_ensemble_reduce");
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "nic_common.h"
+#include "small_ensemble_plan.h"
 #include "small_rollout16.h"
 #include "small_rollout_body.h"
 
@@ -74,13 +75,27 @@ int shape_of(const NicSmallRolloutDesc& d) {
     return 0;
 }
 
-template <int NL, int SHAPE>
+// ENS: K models of one architecture on one batch (nic_small_rollout_ensemble_*): model m = blockIdx.y works on its own slice of
+// every per-model buffer, m x the stride of `es` from the base, with the single-model layout inside; demand, state0 and the tables
+// are shared.  The offsets are scalar arithmetic on the kernel arguments at entry; the period loop is the single-model one.  ENS =
+// false is the single-model kernel as it was (`es` is not read).
+template <int NL, int SHAPE, bool ENS>
 __global__ __launch_bounds__(64) void small_rollout_fwd_mfma_kernel(NicSmallRolloutDesc d, const float* __restrict__ weights,
                                                                     const float* __restrict__ demand,
                                                                     const float* __restrict__ state0, float* __restrict__ rewards,
                                                                     float* __restrict__ state_final, float* __restrict__ states_hist,
-                                                                    float* __restrict__ hidden_hist, float* __restrict__ logits_hist) {
+                                                                    float* __restrict__ hidden_hist, float* __restrict__ logits_hist,
+                                                                    nic::SrFwdStrides es) {
     using namespace nic;
+    if constexpr (ENS) {
+        const int64_t m = blockIdx.y;
+        weights += m * es.weights;
+        rewards += m * es.rewards;
+        state_final += m * es.final_state;
+        states_hist += m * es.states;   // (evaluation: the launcher zeroes the strides of NULL histories, NULL stays NULL)
+        hidden_hist += m * es.hidden;
+        logits_hist += m * es.logits;
+    }
     const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
     const int64_t b_raw = (int64_t)blockIdx.x * 32 + j;
     const bool live = b_raw < d.n_scenarios;
@@ -198,15 +213,25 @@ __global__ __launch_bounds__(64) void small_rollout_fwd_mfma_kernel(NicSmallRoll
 // horizon (one wavefront per SIMD: the register file is otherwise idle, and these MFMA chains are independent of the
 // latency-bound dH chain, whose bubbles they fill).  No dz history is written (97 rows x T x ldb x 4 B for cfg2) or read back.
 // At the end the wavefront stores its partial gradient, in the layout of the packed weights, to `slab[blockIdx.x]`.
-template <int NL, bool WG, int SHAPE>
+// ENS (with WG only): model m = blockIdx.y on its own slices, as in the forward kernel; g_reward is shared.
+template <int NL, bool WG, int SHAPE, bool ENS>
 __global__ __launch_bounds__(64) void small_rollout_bwd_mfma_kernel(NicSmallRolloutDesc d, const float* __restrict__ weights,
                                                                     const float* __restrict__ demand,
                                                                     const float* __restrict__ states_hist,
                                                                     const float* __restrict__ hidden_hist,
                                                                     const float* __restrict__ logits_hist, NicTable2 g_reward,
                                                                     float* __restrict__ dz_hidden, float* __restrict__ dz_out,
-                                                                    float* __restrict__ slab, int64_t slab_stride) {
+                                                                    float* __restrict__ slab, int64_t slab_stride, nic::SrBwdStrides es) {
     using namespace nic;
+    static_assert(WG || !ENS, "the dz-history sweep is single-model");
+    if constexpr (ENS) {
+        const int64_t m = blockIdx.y;
+        weights += m * es.weights;
+        states_hist += m * es.states;
+        hidden_hist += m * es.hidden;
+        logits_hist += m * es.logits;
+        slab += m * es.slab;
+    }
     __shared__ float tiles[WG ? 2 * 32 * 33 : 1];
     float* const tA = tiles;
     float* const tB = tiles + (WG ? 32 * 33 : 0);
@@ -450,6 +475,66 @@ int validate(const NicSmallRolloutDesc* d, const char* who) {
     NIC_REQUIRE(d->E == 0 || (d->ech_holding.p && d->ech_lead.p), "%s: null echelon table", who);
     return 0;
 }
+// the launches behind the single-model and the ensemble entry points: e == nullptr is one model (the single-model instantiations,
+// grid y = 1, no strides), else one grid row per model
+int launch_fwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, float* rewards, float* state_final, float* states_hist,
+               float* hidden_hist, float* logits_hist, hipStream_t s, const char* who) {
+    const int shape = shape_of(*d);
+    if (lane_width(*d, false) == 16) {
+        nic::small_rollout16_fwd(*d, shape, rewards, state_final, states_hist, hidden_hist, logits_hist, s, e);
+        return nic::check_launch(who);
+    }
+    // matrix-core form: 32 scenarios per wavefront
+    if (e) nic::note_kernelf("small_rollout_fwd_mfma_kernel<%d,%s,models=%d>", d->n_hidden, nic::sr_shape_name(shape), e->n_models);
+    else nic::note_kernelf("small_rollout_fwd_mfma_kernel<%d,%s>", d->n_hidden, nic::sr_shape_name(shape));
+    const dim3 g32(nic::ceil_div(d->n_scenarios, 32), e ? e->n_models : 1), b64(64);
+    const nic::SrFwdStrides es = nic::sr_fwd_strides(e, states_hist != nullptr);   // (the kernels add m x stride unconditionally)
+#define NIC_SR_FWD_MFMA_(NL, SH, ENS)                                                                                               \
+    hipLaunchKernelGGL((small_rollout_fwd_mfma_kernel<NL, SH, ENS>), g32, b64, 0, s, *d, d->weights, d->demand, d->state0, rewards, \
+                       state_final, states_hist, hidden_hist, logits_hist, es)
+#define NIC_SR_FWD_MFMA(NL, SH) do { if (e) NIC_SR_FWD_MFMA_(NL, SH, true); else NIC_SR_FWD_MFMA_(NL, SH, false); } while (0)
+    if (shape == 1 && d->n_hidden == 3) NIC_SR_FWD_MFMA(3, 1);
+    else if (shape == 1 && d->n_hidden == 2) NIC_SR_FWD_MFMA(2, 1);
+    else if (shape == 2 && d->n_hidden == 2) NIC_SR_FWD_MFMA(2, 2);
+    else if (shape == 2 && d->n_hidden == 3) NIC_SR_FWD_MFMA(3, 2);
+    else if (d->n_hidden == 1) NIC_SR_FWD_MFMA(1, 0);
+    else if (d->n_hidden == 2) NIC_SR_FWD_MFMA(2, 0);
+    else NIC_SR_FWD_MFMA(3, 0);
+#undef NIC_SR_FWD_MFMA
+#undef NIC_SR_FWD_MFMA_
+    return nic::check_launch(who);
+}
+
+int launch_bwd_wgrad(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const float* states_hist, const float* hidden_hist,
+                     const float* logits_hist, NicTable2 g_reward, float* slab, int64_t slab_stride, hipStream_t s, const char* who) {
+    const int shape = shape_of(*d);
+    if (lane_width(*d, true) == 16) {
+        nic::small_rollout16_bwd_wgrad(*d, shape, states_hist, hidden_hist, logits_hist, g_reward, slab, slab_stride, s, e);
+        return nic::check_launch(who);
+    }
+    if (e) nic::note_kernelf("small_rollout_bwd_mfma_kernel<%d,wgrad,%s,models=%d>", d->n_hidden, nic::sr_shape_name(shape), e->n_models);
+    else nic::note_kernelf("small_rollout_bwd_mfma_kernel<%d,wgrad,%s>", d->n_hidden, nic::sr_shape_name(shape));
+    const dim3 g32(nic::ceil_div(d->n_scenarios, 32), e ? e->n_models : 1), b64(64);
+    const nic::SrBwdStrides es = nic::sr_bwd_strides(e);
+#define NIC_SR_BWD_WG_(NL, SH, ENS)                                                                                                   \
+    hipLaunchKernelGGL((small_rollout_bwd_mfma_kernel<NL, true, SH, ENS>), g32, b64, 0, s, *d, d->weights, d->demand, states_hist, \
+                       hidden_hist, logits_hist, g_reward, (float*)nullptr, (float*)nullptr, slab, slab_stride, es)
+#define NIC_SR_BWD_WG(NL, SH) do { if (e) NIC_SR_BWD_WG_(NL, SH, true); else NIC_SR_BWD_WG_(NL, SH, false); } while (0)
+    if (shape == 1 && d->n_hidden == 3) NIC_SR_BWD_WG(3, 1);
+    else if (shape == 1 && d->n_hidden == 2) NIC_SR_BWD_WG(2, 1);
+    else if (shape == 2 && d->n_hidden == 2) NIC_SR_BWD_WG(2, 2);
+    else if (shape == 2 && d->n_hidden == 3) NIC_SR_BWD_WG(3, 2);
+    else if (d->n_hidden == 1) NIC_SR_BWD_WG(1, 0);
+    else if (d->n_hidden == 2) NIC_SR_BWD_WG(2, 0);
+    else NIC_SR_BWD_WG(3, 0);
+#undef NIC_SR_BWD_WG
+#undef NIC_SR_BWD_WG_
+    return nic::check_launch(who);
+}
+
+NicSmallEnsembleSlices slices_of(const NicSmallRolloutDesc& d) {
+    return nic::small_ensemble_slices(d.n_scenarios, d.ldb, d.T, d.F, d.n_hidden, d.n_out, lane_width(d, true));
+}
 }  // namespace
 
 extern "C" {
@@ -459,28 +544,7 @@ int nic_small_rollout_fwd(const NicSmallRolloutDesc* d, float* rewards, float* s
     if (int e = validate(d, "nic_small_rollout_fwd")) return e;
     NIC_REQUIRE(d->state0 && rewards && state_final, "nic_small_rollout_fwd: null buffer");
     NIC_REQUIRE(!states_hist || (hidden_hist && logits_hist), "nic_small_rollout_fwd: incomplete history buffers");
-    hipStream_t s = nic::as_stream(stream);
-    if (lane_width(*d, false) == 16) {
-        nic::small_rollout16_fwd(*d, shape_of(*d), rewards, state_final, states_hist, hidden_hist, logits_hist, s);
-        return nic::check_launch("nic_small_rollout_fwd");
-    }
-    {  // matrix-core form: 32 scenarios per wavefront
-        const int shape = shape_of(*d);
-        nic::note_kernelf("small_rollout_fwd_mfma_kernel<%d,%s>", d->n_hidden, shape == 1 ? "one_store" : (shape == 2 ? "serial" : "any"));
-        const dim3 g32(nic::ceil_div(d->n_scenarios, 32)), b64(64);
-#define NIC_SR_FWD_MFMA(NL, SH)                                                                                             \
-    hipLaunchKernelGGL((small_rollout_fwd_mfma_kernel<NL, SH>), g32, b64, 0, s, *d, d->weights, d->demand, d->state0, rewards, \
-                       state_final, states_hist, hidden_hist, logits_hist)
-        if (shape == 1 && d->n_hidden == 3) NIC_SR_FWD_MFMA(3, 1);
-        else if (shape == 1 && d->n_hidden == 2) NIC_SR_FWD_MFMA(2, 1);
-        else if (shape == 2 && d->n_hidden == 2) NIC_SR_FWD_MFMA(2, 2);
-        else if (shape == 2 && d->n_hidden == 3) NIC_SR_FWD_MFMA(3, 2);
-        else if (d->n_hidden == 1) NIC_SR_FWD_MFMA(1, 0);
-        else if (d->n_hidden == 2) NIC_SR_FWD_MFMA(2, 0);
-        else NIC_SR_FWD_MFMA(3, 0);
-#undef NIC_SR_FWD_MFMA
-        return nic::check_launch("nic_small_rollout_fwd");
-    }
+    return launch_fwd(d, nullptr, rewards, state_final, states_hist, hidden_hist, logits_hist, nic::as_stream(stream), "nic_small_rollout_fwd");
 }
 
 int nic_small_rollout_bwd(const NicSmallRolloutDesc* d, const float* states_hist, const float* hidden_hist,
@@ -492,11 +556,11 @@ int nic_small_rollout_bwd(const NicSmallRolloutDesc* d, const float* states_hist
     hipStream_t s = nic::as_stream(stream);
     {
         const int shape = shape_of(*d);
-        nic::note_kernelf("small_rollout_bwd_mfma_kernel<%d,%s>", d->n_hidden, shape == 1 ? "one_store" : (shape == 2 ? "serial" : "any"));
+        nic::note_kernelf("small_rollout_bwd_mfma_kernel<%d,%s>", d->n_hidden, nic::sr_shape_name(shape));
         const dim3 g32(nic::ceil_div(d->n_scenarios, 32)), b64(64);
-#define NIC_SR_BWD_MFMA(NL, SH)                                                                                              \
-    hipLaunchKernelGGL((small_rollout_bwd_mfma_kernel<NL, false, SH>), g32, b64, 0, s, *d, d->weights, d->demand, states_hist, \
-                       hidden_hist, logits_hist, g_reward, dz_hidden, dz_out, (float*)nullptr, (int64_t)0)
+#define NIC_SR_BWD_MFMA(NL, SH)                                                                                                     \
+    hipLaunchKernelGGL((small_rollout_bwd_mfma_kernel<NL, false, SH, false>), g32, b64, 0, s, *d, d->weights, d->demand, states_hist, \
+                       hidden_hist, logits_hist, g_reward, dz_hidden, dz_out, (float*)nullptr, (int64_t)0, nic::SrBwdStrides{0, 0, 0, 0, 0})
         if (shape == 1 && d->n_hidden == 3) NIC_SR_BWD_MFMA(3, 1);
         else if (shape == 2 && d->n_hidden == 2) NIC_SR_BWD_MFMA(2, 2);
         else if (d->n_hidden == 1) NIC_SR_BWD_MFMA(1, 0);
@@ -515,28 +579,47 @@ int nic_small_rollout_bwd_wgrad(const NicSmallRolloutDesc* d, const float* state
                                 const float* logits_hist, NicTable2 g_reward, float* slab, int64_t slab_stride, void* stream) {
     if (int e = validate(d, "nic_small_rollout_bwd_wgrad")) return e;
     NIC_REQUIRE(states_hist && hidden_hist && logits_hist && g_reward.p && slab, "nic_small_rollout_bwd_wgrad: null buffer");
-    const int n_packed = (nic::SR_H * d->F + nic::SR_H) + (d->n_hidden - 1) * (nic::SR_H * nic::SR_H + nic::SR_H) + (d->n_out * nic::SR_H + d->n_out);
+    const int n_packed = nic::sr_packed_count(d->F, d->n_hidden, d->n_out);
     NIC_REQUIRE(slab_stride >= n_packed, "nic_small_rollout_bwd_wgrad: slab rows (%lld) shorter than the packed weights (%d)",
                 (long long)slab_stride, n_packed);
-    hipStream_t s = nic::as_stream(stream);
-    const int shape = shape_of(*d);
-    if (lane_width(*d, true) == 16) {
-        nic::small_rollout16_bwd_wgrad(*d, shape, states_hist, hidden_hist, logits_hist, g_reward, slab, slab_stride, s);
-        return nic::check_launch("nic_small_rollout_bwd_wgrad");
-    }
-    nic::note_kernelf("small_rollout_bwd_mfma_kernel<%d,wgrad,%s>", d->n_hidden, shape == 1 ? "one_store" : (shape == 2 ? "serial" : "any"));
-    const dim3 g32(nic::ceil_div(d->n_scenarios, 32)), b64(64);
-#define NIC_SR_BWD_WG(NL, SH)                                                                                                 \
-    hipLaunchKernelGGL((small_rollout_bwd_mfma_kernel<NL, true, SH>), g32, b64, 0, s, *d, d->weights, d->demand, states_hist, \
-                       hidden_hist, logits_hist, g_reward, (float*)nullptr, (float*)nullptr, slab, slab_stride)
-    if (shape == 1 && d->n_hidden == 3) NIC_SR_BWD_WG(3, 1);
-    else if (shape == 1 && d->n_hidden == 2) NIC_SR_BWD_WG(2, 1);
-    else if (shape == 2 && d->n_hidden == 2) NIC_SR_BWD_WG(2, 2);
-    else if (shape == 2 && d->n_hidden == 3) NIC_SR_BWD_WG(3, 2);
-    else if (d->n_hidden == 1) NIC_SR_BWD_WG(1, 0);
-    else if (d->n_hidden == 2) NIC_SR_BWD_WG(2, 0);
-    else NIC_SR_BWD_WG(3, 0);
-#undef NIC_SR_BWD_WG
-    return nic::check_launch("nic_small_rollout_bwd_wgrad");
+    return launch_bwd_wgrad(d, nullptr, states_hist, hidden_hist, logits_hist, g_reward, slab, slab_stride, nic::as_stream(stream),
+                            "nic_small_rollout_bwd_wgrad");
+}
+
+/* ---- K models in one launch (csrc/small_ensemble_plan.h holds the slice sizes and the checks) ---- */
+int nic_small_rollout_ensemble_slices(const NicSmallRolloutDesc* d, NicSmallEnsembleSlices* out) {
+    NIC_REQUIRE(d != nullptr && out != nullptr, "nic_small_rollout_ensemble_slices: null argument");
+    NIC_REQUIRE(d->n_scenarios > 0 && d->ldb >= d->n_scenarios && d->T > 0 && d->F >= 1 && d->F <= NIC_SR_MAX_INPUTS && d->n_hidden >= 1 &&
+                    d->n_hidden <= 3 && d->n_out >= 1 && d->n_out <= NIC_SR_MAX_OUTPUTS,
+                "nic_small_rollout_ensemble_slices: bad sizes");
+    NIC_REQUIRE(d->lane_scenarios == 0 || d->lane_scenarios == 16 || d->lane_scenarios == 32,
+                "nic_small_rollout_ensemble_slices: lane_scenarios must be 0, 16 or 32");
+    *out = slices_of(*d);
+    return 0;
+}
+
+int nic_small_rollout_ensemble_fwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, float* rewards, float* state_final,
+                                   float* states_hist, float* hidden_hist, float* logits_hist, void* stream) {
+    if (int r = validate(d, "nic_small_rollout_ensemble_fwd")) return r;
+    NIC_REQUIRE(e != nullptr, "nic_small_rollout_ensemble_fwd: null ensemble");
+    NIC_REQUIRE(d->state0 && rewards && state_final, "nic_small_rollout_ensemble_fwd: null buffer");
+    NIC_REQUIRE((states_hist != nullptr) == (hidden_hist != nullptr) && (states_hist != nullptr) == (logits_hist != nullptr),
+                "nic_small_rollout_ensemble_fwd: incomplete history buffers");
+    const int why = nic::small_ensemble_check_fwd(*e, slices_of(*d), states_hist != nullptr);
+    NIC_REQUIRE(why == 0, "nic_small_rollout_ensemble_fwd: %s (%d models)", nic::small_ensemble_reason(why), e->n_models);
+    return launch_fwd(d, e, rewards, state_final, states_hist, hidden_hist, logits_hist, nic::as_stream(stream), "nic_small_rollout_ensemble_fwd");
+}
+
+int nic_small_rollout_ensemble_bwd_wgrad(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const float* states_hist,
+                                         const float* hidden_hist, const float* logits_hist, NicTable2 g_reward, float* slab,
+                                         int64_t slab_row_stride, void* stream) {
+    if (int r = validate(d, "nic_small_rollout_ensemble_bwd_wgrad")) return r;
+    NIC_REQUIRE(e != nullptr, "nic_small_rollout_ensemble_bwd_wgrad: null ensemble");
+    NIC_REQUIRE(states_hist && hidden_hist && logits_hist && g_reward.p && slab, "nic_small_rollout_ensemble_bwd_wgrad: null buffer");
+    const int why = nic::small_ensemble_check_bwd(*e, slices_of(*d), slab_row_stride);
+    NIC_REQUIRE(why == 0, "nic_small_rollout_ensemble_bwd_wgrad: %s (%d models, slab rows of %lld)", nic::small_ensemble_reason(why),
+                e->n_models, (long long)slab_row_stride);
+    return launch_bwd_wgrad(d, e, states_hist, hidden_hist, logits_hist, g_reward, slab, slab_row_stride, nic::as_stream(stream),
+                            "nic_small_rollout_ensemble_bwd_wgrad");
 }
 }

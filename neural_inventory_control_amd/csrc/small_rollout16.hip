@@ -92,13 +92,27 @@ __device__ __forceinline__ void layer32(const float (&aW)[2][8], const float (&b
     }
 }
 
-template <int NL, int SHAPE>
+// ENS: K models of one architecture on one batch, model m = blockIdx.y on its own slice of every per-model buffer (m x the stride
+// of `es`, single-model layout inside a slice; demand, state0 and the tables are shared).  The offsets are wave-uniform - scalar
+// arithmetic on the kernel arguments before the first load - and nothing in the period loop knows of them.  ENS = false is the
+// single-model kernel as it was (`es` is not read).
+template <int NL, int SHAPE, bool ENS>
 __global__ __launch_bounds__(64, 2) void small_rollout16_fwd_kernel(NicSmallRolloutDesc d, const float* __restrict__ weights,
                                                                     const float* __restrict__ demand,
                                                                     const float* __restrict__ state0, float* __restrict__ rewards,
                                                                     float* __restrict__ state_final, float* __restrict__ states_hist,
-                                                                    float* __restrict__ hidden_hist, float* __restrict__ logits_hist) {
+                                                                    float* __restrict__ hidden_hist, float* __restrict__ logits_hist,
+                                                                    nic::SrFwdStrides es) {
     using namespace nic;
+    if constexpr (ENS) {
+        const int64_t m = blockIdx.y;
+        weights += m * es.weights;
+        rewards += m * es.rewards;
+        state_final += m * es.final_state;
+        states_hist += m * es.states;   // (evaluation: the launcher zeroes the strides of NULL histories, NULL stays NULL)
+        hidden_hist += m * es.hidden;
+        logits_hist += m * es.logits;
+    }
     const int lane = threadIdx.x, j = lane & 15, g = lane >> 4;
     const int64_t b_raw = (int64_t)blockIdx.x * 16 + j;
     const bool live = b_raw < d.n_scenarios;
@@ -225,14 +239,22 @@ __global__ __launch_bounds__(64, 2) void small_rollout16_fwd_kernel(NicSmallRoll
 // per period and layer the pre-activation gradient and the layer input go through two wave-private LDS tiles ([32 rows][16
 // scenarios], row stride 17) into row-owner operands, and 16 MFMAs (4 output tiles x 4 steps of 4 scenarios) add dZ X^T into
 // accumulators that stay in registers for the whole horizon.
-template <int NL, int SHAPE>
+template <int NL, int SHAPE, bool ENS>
 __global__ __launch_bounds__(64, 2) void small_rollout16_bwd_kernel(NicSmallRolloutDesc d, const float* __restrict__ weights,
                                                                  const float* __restrict__ demand,
                                                                  const float* __restrict__ states_hist,
                                                                  const float* __restrict__ hidden_hist,
                                                                  const float* __restrict__ logits_hist, NicTable2 g_reward,
-                                                                 float* __restrict__ slab, int64_t slab_stride) {
+                                                                 float* __restrict__ slab, int64_t slab_stride, nic::SrBwdStrides es) {
     using namespace nic;
+    if constexpr (ENS) {   // (model m = blockIdx.y on its own slices, see the forward kernel; g_reward is shared)
+        const int64_t m = blockIdx.y;
+        weights += m * es.weights;
+        states_hist += m * es.states;
+        hidden_hist += m * es.hidden;
+        logits_hist += m * es.logits;
+        slab += m * es.slab;
+    }
     constexpr int NH = NL > 1 ? NL - 1 : 1;
     __shared__ float tiles[2 * 32 * 17];
     float* const tA = tiles;
@@ -506,13 +528,17 @@ extern "C" int nic_tuning_set_small_rollout_stamps(void* buf) {   // buf: device
 
 namespace nic {
 
+// e == nullptr: the single-model kernels (grid y = 1, no strides); else the ensemble instantiations, one grid row per model
 void small_rollout16_fwd(const NicSmallRolloutDesc& d, int shape, float* rewards, float* state_final, float* states_hist,
-                         float* hidden_hist, float* logits_hist, hipStream_t s) {
-    nic::note_kernelf("small_rollout16_fwd_kernel<%d,%s>", d.n_hidden, shape == 1 ? "one_store" : (shape == 2 ? "serial" : "any"));
-    const dim3 grid(nic::ceil_div(d.n_scenarios, 16)), block(64);
-#define NIC_SR16_FWD(NL, SH)                                                                                              \
-    hipLaunchKernelGGL((small_rollout16_fwd_kernel<NL, SH>), grid, block, 0, s, d, d.weights, d.demand, d.state0, rewards,  \
-                       state_final, states_hist, hidden_hist, logits_hist)
+                         float* hidden_hist, float* logits_hist, hipStream_t s, const NicSmallEnsemble* e) {
+    if (e) nic::note_kernelf("small_rollout16_fwd_kernel<%d,%s,models=%d>", d.n_hidden, nic::sr_shape_name(shape), e->n_models);
+    else nic::note_kernelf("small_rollout16_fwd_kernel<%d,%s>", d.n_hidden, nic::sr_shape_name(shape));
+    const dim3 grid(nic::ceil_div(d.n_scenarios, 16), e ? e->n_models : 1), block(64);
+    const nic::SrFwdStrides es = nic::sr_fwd_strides(e, states_hist != nullptr);   // (the kernels add m x stride unconditionally)
+#define NIC_SR16_FWD_(NL, SH, ENS)                                                                                              \
+    hipLaunchKernelGGL((small_rollout16_fwd_kernel<NL, SH, ENS>), grid, block, 0, s, d, d.weights, d.demand, d.state0, rewards, \
+                       state_final, states_hist, hidden_hist, logits_hist, es)
+#define NIC_SR16_FWD(NL, SH) do { if (e) NIC_SR16_FWD_(NL, SH, true); else NIC_SR16_FWD_(NL, SH, false); } while (0)
     if (shape == 1 && d.n_hidden == 3) NIC_SR16_FWD(3, 1);
     else if (shape == 1 && d.n_hidden == 2) NIC_SR16_FWD(2, 1);
     else if (shape == 2 && d.n_hidden == 2) NIC_SR16_FWD(2, 2);
@@ -521,15 +547,20 @@ void small_rollout16_fwd(const NicSmallRolloutDesc& d, int shape, float* rewards
     else if (d.n_hidden == 2) NIC_SR16_FWD(2, 0);
     else NIC_SR16_FWD(3, 0);
 #undef NIC_SR16_FWD
+#undef NIC_SR16_FWD_
 }
 
 void small_rollout16_bwd_wgrad(const NicSmallRolloutDesc& d, int shape, const float* states_hist, const float* hidden_hist,
-                               const float* logits_hist, NicTable2 g_reward, float* slab, int64_t slab_stride, hipStream_t s) {
-    nic::note_kernelf("small_rollout16_bwd_kernel<%d,wgrad,%s>", d.n_hidden, shape == 1 ? "one_store" : (shape == 2 ? "serial" : "any"));
-    const dim3 grid(nic::ceil_div(d.n_scenarios, 16)), block(64);
-#define NIC_SR16_BWD(NL, SH)                                                                                               \
-    hipLaunchKernelGGL((small_rollout16_bwd_kernel<NL, SH>), grid, block, 0, s, d, d.weights, d.demand, states_hist, hidden_hist, \
-                       logits_hist, g_reward, slab, slab_stride)
+                               const float* logits_hist, NicTable2 g_reward, float* slab, int64_t slab_stride, hipStream_t s,
+                               const NicSmallEnsemble* e) {
+    if (e) nic::note_kernelf("small_rollout16_bwd_kernel<%d,wgrad,%s,models=%d>", d.n_hidden, nic::sr_shape_name(shape), e->n_models);
+    else nic::note_kernelf("small_rollout16_bwd_kernel<%d,wgrad,%s>", d.n_hidden, nic::sr_shape_name(shape));
+    const dim3 grid(nic::ceil_div(d.n_scenarios, 16), e ? e->n_models : 1), block(64);
+    const nic::SrBwdStrides es = nic::sr_bwd_strides(e);
+#define NIC_SR16_BWD_(NL, SH, ENS)                                                                                                     \
+    hipLaunchKernelGGL((small_rollout16_bwd_kernel<NL, SH, ENS>), grid, block, 0, s, d, d.weights, d.demand, states_hist, hidden_hist, \
+                       logits_hist, g_reward, slab, slab_stride, es)
+#define NIC_SR16_BWD(NL, SH) do { if (e) NIC_SR16_BWD_(NL, SH, true); else NIC_SR16_BWD_(NL, SH, false); } while (0)
     if (shape == 1 && d.n_hidden == 3) NIC_SR16_BWD(3, 1);
     else if (shape == 1 && d.n_hidden == 2) NIC_SR16_BWD(2, 1);
     else if (shape == 2 && d.n_hidden == 2) NIC_SR16_BWD(2, 2);
@@ -538,6 +569,7 @@ void small_rollout16_bwd_wgrad(const NicSmallRolloutDesc& d, int shape, const fl
     else if (d.n_hidden == 2) NIC_SR16_BWD(2, 0);
     else NIC_SR16_BWD(3, 0);
 #undef NIC_SR16_BWD
+#undef NIC_SR16_BWD_
 }
 
 }  // namespace nic

@@ -126,3 +126,50 @@ def small_rollout_reduce(slab, n_rows, grad, rewards, ignore_periods, totals, sc
                                                    _lib.ptr(grad), _lib.ptr(rewards), n_el,
                                                    int(ignore_periods) * rewards.shape[-1] if rewards is not None else 0,
                                                    _lib.ptr(totals), _lib.ptr(scratch), _lib.current_stream()))
+
+
+# ---- K models of one architecture on one batch (nic_small_rollout_ensemble_*, csrc/small_ensemble_plan.h) ----------------------------
+SLICE_FIELDS = tuple(n for n, _ in _lib.NicSmallEnsembleSlices._fields_)
+STRIDE_FIELDS = tuple(n for n, _ in _lib.NicSmallEnsemble._fields_[2:])
+
+
+def ensemble_slices(desc):
+    """{buffer: floats of ONE model's slice} for a descriptor (its lane_scenarios decides the history rows) - the numbers the entry
+    points check the strides against, from csrc/small_ensemble_plan.h.  Needs the library, not a device."""
+    out = _lib.NicSmallEnsembleSlices()
+    _lib.check(_lib.lib().nic_small_rollout_ensemble_slices(desc, out))
+    return {n: int(getattr(out, n)) for n in SLICE_FIELDS}
+
+
+def ensemble_strides(n_models, **strides):
+    """NicSmallEnsemble: floats between two models' slices of every per-model buffer (buffers a call does not take: 0)."""
+    e = _lib.NicSmallEnsemble()
+    e.n_models = int(n_models)
+    for k, v in strides.items():
+        if k not in STRIDE_FIELDS:
+            raise KeyError(k)
+        setattr(e, k, int(v))
+    return e
+
+
+def small_rollout_ensemble_fwd(desc, ens, rewards, state_final, states_hist, hidden_hist, logits_hist):
+    ops._dev(rewards)
+    _lib.check(_lib.lib().nic_small_rollout_ensemble_fwd(desc, ens, _lib.ptr(rewards), _lib.ptr(state_final), _lib.ptr(states_hist),
+                                                         _lib.ptr(hidden_hist), _lib.ptr(logits_hist), _lib.current_stream()))
+
+
+def small_rollout_ensemble_bwd_wgrad(desc, ens, states_hist, hidden_hist, logits_hist, g_reward: Table, slab, slab_row_stride):
+    """slab [K][>= rows x slab_row_stride]: model m's wavefront w writes its partial gradient at m * ens.slab + w * slab_row_stride."""
+    ops._dev(slab)
+    _lib.check(_lib.lib().nic_small_rollout_ensemble_bwd_wgrad(desc, ens, _lib.ptr(states_hist), _lib.ptr(hidden_hist),
+                                                               _lib.ptr(logits_hist), g_reward.t2(), _lib.ptr(slab),
+                                                               int(slab_row_stride), _lib.current_stream()))
+
+
+def small_rollout_ensemble_reduce(ens, slab, n_rows, slab_row_stride, P, grad, rewards, n_reward_elems, ignore_elems, totals, scratch):
+    """grad [K][ens.grad] <- column sums of every model's first n_rows slab rows; totals [K][2] <- every model's total / reported
+    cost: `nic_small_rollout_reduce` for all K models in its two launches.  Either pair may be None."""
+    ops._dev(scratch)
+    _lib.check(_lib.lib().nic_small_rollout_ensemble_reduce(ens, _lib.ptr(slab), int(n_rows), int(slab_row_stride), int(P), _lib.ptr(grad),
+                                                            _lib.ptr(rewards), int(n_reward_elems), int(ignore_elems),
+                                                            _lib.ptr(totals), _lib.ptr(scratch), _lib.current_stream()))
