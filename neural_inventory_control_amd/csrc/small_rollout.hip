@@ -13,6 +13,7 @@
 #include "small_ensemble_plan.h"
 #include "small_rollout16.h"
 #include "small_rollout_body.h"
+#include "small_rollout_mfma.h"
 
 namespace {
 constexpr int kBlock = 64;
@@ -30,49 +31,10 @@ constexpr int kBlock = 64;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 __device__ __forceinline__ int crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
-// ELU of an accumulator: the series of nic::expm1_neg on PAIRS of elements with packed FP32 FMAs (v_pk_fma_f32: two lanes' worth
-// of work per instruction; each component rounds exactly like the scalar fmaf chain, so the values are those of nic::elu1).  The
-// activations are more than half of the forward kernel's instruction stream (48 per scenario-period).
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+// ELU of an accumulator (same values as nic::elu1)
 __device__ __forceinline__ void elu16(const f32x16& z, float (&out)[16]) {
 #pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-        const f32x2 x = {z[r], z[r + 1]};
-        f32x2 p = __builtin_elementwise_fma(x, (f32x2)(1.f / 720.f), (f32x2)(1.f / 120.f));
-        p = __builtin_elementwise_fma(x, p, (f32x2)(1.f / 24.f));
-        p = __builtin_elementwise_fma(x, p, (f32x2)(1.f / 6.f));
-        p = __builtin_elementwise_fma(x, p, (f32x2)(0.5f));
-        p = __builtin_elementwise_fma(x, p, (f32x2)(1.f));
-        const f32x2 sp = x * p;
-        const float e0 = __expf(x.x) - 1.f, e1 = __expf(x.y) - 1.f;
-        const float n0 = x.x > -0.35f ? sp.x : e0, n1 = x.y > -0.35f ? sp.y : e1;
-        out[r] = x.x > 0.f ? x.x : n0;
-        out[r + 1] = x.y > 0.f ? x.y : n1;
-    }
-}
-
-// Shape specialisation.  The per-lane env step / head bodies (small_rollout_body.h) index the st[16] register array with offsets
-// built from the descriptor's pipeline lengths; with those as run-time values every access is a 16-way select chain whose 64-bit
-// lane masks live in (spilled) SGPRs - 4,100 instructions per period, a quarter of them v_readlane / s_nop spill traffic, on a
-// kernel whose duration IS the instruction count of one wavefront (one wave per SIMD, T sequential periods).  The two chains the
-// reference ships are therefore compiled with their structure as constants: overwriting the structural fields of the kernel's
-// own copy of the descriptor lets constant propagation fold every offset, loop bound and select through the always-inline bodies.
-//   SHAPE 0: any supported chain (run-time structure)
-//   SHAPE 1: one store, Ws = 4, softplus head            (one_store_lost.yml / one_store_backlogged.yml + vanilla_one_store)
-//   SHAPE 2: store + warehouse + 2 echelons, 4 / 3 / 4, serial head   (serial_system.yml + vanilla_serial)
-template <int SHAPE>
-__device__ __forceinline__ void fix_shape(NicSmallRolloutDesc& d, int n_hidden) {
-    d.n_hidden = n_hidden;
-    if (SHAPE == 1) {
-        d.Ws = 4; d.Ww = 0; d.We = 0; d.Wn = 0; d.E = 0; d.head = 0; d.F = 4; d.n_out = 1;
-    } else if (SHAPE == 2) {
-        d.Ws = 4; d.Ww = 3; d.We = 4; d.Wn = 1; d.E = 2; d.head = 1; d.F = 15; d.n_out = 4;
-    }
-}
-int shape_of(const NicSmallRolloutDesc& d) {
-    if (d.Ws == 4 && d.Wn == 0 && d.E == 0 && d.head == 0 && d.F == 4 && d.n_out == 1) return 1;
-    if (d.Ws == 4 && d.Wn == 1 && d.Ww == 3 && d.E == 2 && d.We == 4 && d.head == 1 && d.F == 15 && d.n_out == 4) return 2;
-    return 0;
+    for (int r = 0; r < 16; r += 2) nic::sr_elu_pair(z[r], z[r + 1], out[r], out[r + 1]);
 }
 
 // ENS: K models of one architecture on one batch (nic_small_rollout_ensemble_*): model m = blockIdx.y works on its own slice of
@@ -104,7 +66,7 @@ __global__ __launch_bounds__(64) void small_rollout_fwd_mfma_kernel(NicSmallRoll
     d.weights = weights;
     d.demand = demand;
     d.state0 = state0;
-    fix_shape<SHAPE>(d, NL);
+    sr_fix_shape<SHAPE>(d, NL);
 
     // ---- weight fragments, resident for the whole horizon
     const int i = j;  // A-operand row owned by this lane
@@ -242,7 +204,7 @@ __global__ __launch_bounds__(64) void small_rollout_bwd_mfma_kernel(NicSmallRoll
     const int64_t ldb = d.ldb, tl = (int64_t)d.T * ldb;
     d.weights = weights;
     d.demand = demand;
-    fix_shape<SHAPE>(d, NL);
+    sr_fix_shape<SHAPE>(d, NL);
 
     const int i = j;  // A-operand row: the INPUT feature of the layer being back-propagated through
     float aWoT[4], aWhT[(NL > 1 ? NL - 1 : 1)][16], aW1T[16];
@@ -454,17 +416,24 @@ __global__ __launch_bounds__(64) void small_rollout_bwd_mfma_kernel(NicSmallRoll
     }
 }
 
-// scenarios per wavefront: 32 unless the descriptor asks for the 16-scenario form (whose hidden-activation history is in a
-// wave-native order private to its forward / backward pair, so the choice is the caller's and the same for both launches)
-int lane_width(const NicSmallRolloutDesc& d, bool) { return d.lane_scenarios == 16 ? 16 : 32; }
+// what `validate` and the slices query both check of a descriptor (each words its own refusal): the first fault, in this order
+enum SizeFault { SIZES_OK = 0, BAD_BATCH, BAD_N_HIDDEN, BAD_N_OUT, BAD_LANES };
+SizeFault size_fault(const NicSmallRolloutDesc& d) {
+    if (!(d.n_scenarios > 0 && d.ldb >= d.n_scenarios && d.T > 0)) return BAD_BATCH;
+    if (!(d.n_hidden >= 1 && d.n_hidden <= 3)) return BAD_N_HIDDEN;
+    if (!(d.n_out >= 1 && d.n_out <= NIC_SR_MAX_OUTPUTS)) return BAD_N_OUT;
+    if (!(d.lane_scenarios == 0 || d.lane_scenarios == 16 || d.lane_scenarios == 32)) return BAD_LANES;
+    return SIZES_OK;
+}
 
 int validate(const NicSmallRolloutDesc* d, const char* who) {
     NIC_REQUIRE(d != nullptr, "%s: null descriptor", who);
-    NIC_REQUIRE(d->n_scenarios > 0 && d->ldb >= d->n_scenarios && d->T > 0 && d->t0 >= 0, "%s: bad sizes", who);
-    NIC_REQUIRE(d->n_hidden >= 1 && d->n_hidden <= 3, "%s: n_hidden must be 1..3", who);
-    NIC_REQUIRE(d->n_out >= 1 && d->n_out <= NIC_SR_MAX_OUTPUTS, "%s: n_out out of range", who);
+    const SizeFault fault = size_fault(*d);
+    NIC_REQUIRE(fault != BAD_BATCH && d->t0 >= 0, "%s: bad sizes", who);
+    NIC_REQUIRE(fault != BAD_N_HIDDEN, "%s: n_hidden must be 1..3", who);
+    NIC_REQUIRE(fault != BAD_N_OUT, "%s: n_out out of range", who);
     NIC_REQUIRE(d->head == 0 || d->head == 1, "%s: unknown head", who);
-    NIC_REQUIRE(d->lane_scenarios == 0 || d->lane_scenarios == 16 || d->lane_scenarios == 32, "%s: lane_scenarios must be 0, 16 or 32", who);
+    NIC_REQUIRE(fault != BAD_LANES, "%s: lane_scenarios must be 0, 16 or 32", who);
     NIC_REQUIRE(d->lane_scenarios != 16 || d->ldb % 16 == 0, "%s: the 16-scenario form needs ldb to be a multiple of 16", who);
     NIC_REQUIRE(d->Ws >= 2 && d->Wn >= 0 && d->Wn <= 1 && d->E >= 0 && d->E <= 3, "%s: unsupported chain", who);
     NIC_REQUIRE(d->E == 0 || d->Wn == 1, "%s: echelons need the warehouse", who);
@@ -475,65 +444,55 @@ int validate(const NicSmallRolloutDesc* d, const char* who) {
     NIC_REQUIRE(d->E == 0 || (d->ech_holding.p && d->ech_lead.p), "%s: null echelon table", who);
     return 0;
 }
-// the launches behind the single-model and the ensemble entry points: e == nullptr is one model (the single-model instantiations,
-// grid y = 1, no strides), else one grid row per model
+
+// The launches behind the entry points: grid and strides, the recorded name, then the instantiation small_rollout_variants.h picks.
+// e == nullptr is one model (the single-model instantiations, grid y = 1, no strides), else one grid row per model.
 int launch_fwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, float* rewards, float* state_final, float* states_hist,
                float* hidden_hist, float* logits_hist, hipStream_t s, const char* who) {
-    const int shape = shape_of(*d);
-    if (lane_width(*d, false) == 16) {
-        nic::small_rollout16_fwd(*d, shape, rewards, state_final, states_hist, hidden_hist, logits_hist, s, e);
-        return nic::check_launch(who);
+    using namespace nic;
+    const int shape = sr_shape_of(*d);
+    bool launched;
+    if (sr_lane_width(*d) == 16) {
+        launched = small_rollout16_fwd(*d, shape, rewards, state_final, states_hist, hidden_hist, logits_hist, s, e);
+    } else {   // matrix-core form: 32 scenarios per wavefront
+        const dim3 g32(ceil_div(d->n_scenarios, 32), e ? e->n_models : 1), b64(64);
+        const SrFwdStrides es = sr_fwd_strides(e, states_hist != nullptr);   // (the kernels add m x stride unconditionally)
+        sr_note_kernel(SR_FWD, *d, shape, e);
+        launched = sr_dispatch<SR_FWD>(sr_variant(SR_FWD, shape, d->n_hidden), e != nullptr, [&](auto nl, auto sh, auto ens) {
+            hipLaunchKernelGGL((small_rollout_fwd_mfma_kernel<nl(), sh(), ens()>), g32, b64, 0, s, *d, d->weights, d->demand, d->state0,
+                               rewards, state_final, states_hist, hidden_hist, logits_hist, es);
+        });
     }
-    // matrix-core form: 32 scenarios per wavefront
-    if (e) nic::note_kernelf("small_rollout_fwd_mfma_kernel<%d,%s,models=%d>", d->n_hidden, nic::sr_shape_name(shape), e->n_models);
-    else nic::note_kernelf("small_rollout_fwd_mfma_kernel<%d,%s>", d->n_hidden, nic::sr_shape_name(shape));
-    const dim3 g32(nic::ceil_div(d->n_scenarios, 32), e ? e->n_models : 1), b64(64);
-    const nic::SrFwdStrides es = nic::sr_fwd_strides(e, states_hist != nullptr);   // (the kernels add m x stride unconditionally)
-#define NIC_SR_FWD_MFMA_(NL, SH, ENS)                                                                                               \
-    hipLaunchKernelGGL((small_rollout_fwd_mfma_kernel<NL, SH, ENS>), g32, b64, 0, s, *d, d->weights, d->demand, d->state0, rewards, \
-                       state_final, states_hist, hidden_hist, logits_hist, es)
-#define NIC_SR_FWD_MFMA(NL, SH) do { if (e) NIC_SR_FWD_MFMA_(NL, SH, true); else NIC_SR_FWD_MFMA_(NL, SH, false); } while (0)
-    if (shape == 1 && d->n_hidden == 3) NIC_SR_FWD_MFMA(3, 1);
-    else if (shape == 1 && d->n_hidden == 2) NIC_SR_FWD_MFMA(2, 1);
-    else if (shape == 2 && d->n_hidden == 2) NIC_SR_FWD_MFMA(2, 2);
-    else if (shape == 2 && d->n_hidden == 3) NIC_SR_FWD_MFMA(3, 2);
-    else if (d->n_hidden == 1) NIC_SR_FWD_MFMA(1, 0);
-    else if (d->n_hidden == 2) NIC_SR_FWD_MFMA(2, 0);
-    else NIC_SR_FWD_MFMA(3, 0);
-#undef NIC_SR_FWD_MFMA
-#undef NIC_SR_FWD_MFMA_
-    return nic::check_launch(who);
+    NIC_REQUIRE(launched, "%s: no kernel for n_hidden = %d", who, d->n_hidden);
+    return check_launch(who);
 }
 
-int launch_bwd_wgrad(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const float* states_hist, const float* hidden_hist,
-                     const float* logits_hist, NicTable2 g_reward, float* slab, int64_t slab_stride, hipStream_t s, const char* who) {
-    const int shape = shape_of(*d);
-    if (lane_width(*d, true) == 16) {
-        nic::small_rollout16_bwd_wgrad(*d, shape, states_hist, hidden_hist, logits_hist, g_reward, slab, slab_stride, s, e);
-        return nic::check_launch(who);
+// WG = true: in-kernel weight gradients into `slab` (either width, one model or K); false: the dz-history sweep (dz_hidden, dz_out)
+template <bool WG>
+int launch_bwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const float* states_hist, const float* hidden_hist,
+               const float* logits_hist, NicTable2 g_reward, float* dz_hidden, float* dz_out, float* slab, int64_t slab_stride,
+               hipStream_t s, const char* who) {
+    using namespace nic;
+    constexpr SrRoute route = WG ? SR_BWD_WGRAD : SR_BWD_DZ;
+    const int shape = sr_shape_of(*d);
+    bool launched;
+    if (WG && sr_lane_width(*d) == 16) {
+        launched = small_rollout16_bwd_wgrad(*d, shape, states_hist, hidden_hist, logits_hist, g_reward, slab, slab_stride, s, e);
+    } else {
+        const dim3 g32(ceil_div(d->n_scenarios, 32), e ? e->n_models : 1), b64(64);
+        const SrBwdStrides es = sr_bwd_strides(e);
+        sr_note_kernel(route, *d, shape, e);
+        launched = sr_dispatch<route>(sr_variant(route, shape, d->n_hidden), e != nullptr, [&](auto nl, auto sh, auto ens) {
+            hipLaunchKernelGGL((small_rollout_bwd_mfma_kernel<nl(), WG, sh(), ens()>), g32, b64, 0, s, *d, d->weights, d->demand,
+                               states_hist, hidden_hist, logits_hist, g_reward, dz_hidden, dz_out, slab, slab_stride, es);
+        });
     }
-    if (e) nic::note_kernelf("small_rollout_bwd_mfma_kernel<%d,wgrad,%s,models=%d>", d->n_hidden, nic::sr_shape_name(shape), e->n_models);
-    else nic::note_kernelf("small_rollout_bwd_mfma_kernel<%d,wgrad,%s>", d->n_hidden, nic::sr_shape_name(shape));
-    const dim3 g32(nic::ceil_div(d->n_scenarios, 32), e ? e->n_models : 1), b64(64);
-    const nic::SrBwdStrides es = nic::sr_bwd_strides(e);
-#define NIC_SR_BWD_WG_(NL, SH, ENS)                                                                                                   \
-    hipLaunchKernelGGL((small_rollout_bwd_mfma_kernel<NL, true, SH, ENS>), g32, b64, 0, s, *d, d->weights, d->demand, states_hist, \
-                       hidden_hist, logits_hist, g_reward, (float*)nullptr, (float*)nullptr, slab, slab_stride, es)
-#define NIC_SR_BWD_WG(NL, SH) do { if (e) NIC_SR_BWD_WG_(NL, SH, true); else NIC_SR_BWD_WG_(NL, SH, false); } while (0)
-    if (shape == 1 && d->n_hidden == 3) NIC_SR_BWD_WG(3, 1);
-    else if (shape == 1 && d->n_hidden == 2) NIC_SR_BWD_WG(2, 1);
-    else if (shape == 2 && d->n_hidden == 2) NIC_SR_BWD_WG(2, 2);
-    else if (shape == 2 && d->n_hidden == 3) NIC_SR_BWD_WG(3, 2);
-    else if (d->n_hidden == 1) NIC_SR_BWD_WG(1, 0);
-    else if (d->n_hidden == 2) NIC_SR_BWD_WG(2, 0);
-    else NIC_SR_BWD_WG(3, 0);
-#undef NIC_SR_BWD_WG
-#undef NIC_SR_BWD_WG_
-    return nic::check_launch(who);
+    NIC_REQUIRE(launched, "%s: no kernel for n_hidden = %d", who, d->n_hidden);
+    return check_launch(who);
 }
 
 NicSmallEnsembleSlices slices_of(const NicSmallRolloutDesc& d) {
-    return nic::small_ensemble_slices(d.n_scenarios, d.ldb, d.T, d.F, d.n_hidden, d.n_out, lane_width(d, true));
+    return nic::small_ensemble_slices(d.n_scenarios, d.ldb, d.T, d.F, d.n_hidden, d.n_out, nic::sr_lane_width(d));
 }
 }  // namespace
 
@@ -547,30 +506,6 @@ int nic_small_rollout_fwd(const NicSmallRolloutDesc* d, float* rewards, float* s
     return launch_fwd(d, nullptr, rewards, state_final, states_hist, hidden_hist, logits_hist, nic::as_stream(stream), "nic_small_rollout_fwd");
 }
 
-int nic_small_rollout_bwd(const NicSmallRolloutDesc* d, const float* states_hist, const float* hidden_hist,
-                          const float* logits_hist, NicTable2 g_reward, float* dz_hidden, float* dz_out, void* stream) {
-    if (int e = validate(d, "nic_small_rollout_bwd")) return e;
-    NIC_REQUIRE(d->lane_scenarios != 16, "nic_small_rollout_bwd: the dz-history sweep reads the [row][t][ldb] history of the 32-scenario forward");
-    NIC_REQUIRE(states_hist && hidden_hist && logits_hist && g_reward.p && dz_hidden && dz_out,
-                "nic_small_rollout_bwd: null buffer");
-    hipStream_t s = nic::as_stream(stream);
-    {
-        const int shape = shape_of(*d);
-        nic::note_kernelf("small_rollout_bwd_mfma_kernel<%d,%s>", d->n_hidden, nic::sr_shape_name(shape));
-        const dim3 g32(nic::ceil_div(d->n_scenarios, 32)), b64(64);
-#define NIC_SR_BWD_MFMA(NL, SH)                                                                                                     \
-    hipLaunchKernelGGL((small_rollout_bwd_mfma_kernel<NL, false, SH, false>), g32, b64, 0, s, *d, d->weights, d->demand, states_hist, \
-                       hidden_hist, logits_hist, g_reward, dz_hidden, dz_out, (float*)nullptr, (int64_t)0, nic::SrBwdStrides{0, 0, 0, 0, 0})
-        if (shape == 1 && d->n_hidden == 3) NIC_SR_BWD_MFMA(3, 1);
-        else if (shape == 2 && d->n_hidden == 2) NIC_SR_BWD_MFMA(2, 2);
-        else if (d->n_hidden == 1) NIC_SR_BWD_MFMA(1, 0);
-        else if (d->n_hidden == 2) NIC_SR_BWD_MFMA(2, 0);
-        else NIC_SR_BWD_MFMA(3, 0);
-#undef NIC_SR_BWD_MFMA
-        return nic::check_launch("nic_small_rollout_bwd");
-    }
-}
-
 /* (one partial-gradient row per wavefront; sized for the 16-scenario form - the 32-scenario form fills the first half and the
  * caller's buffer is zero elsewhere) */
 int nic_small_rollout_bwd_wgrad_slots(int32_t n_scenarios) { return nic::ceil_div(n_scenarios, 16); }
@@ -582,18 +517,27 @@ int nic_small_rollout_bwd_wgrad(const NicSmallRolloutDesc* d, const float* state
     const int n_packed = nic::sr_packed_count(d->F, d->n_hidden, d->n_out);
     NIC_REQUIRE(slab_stride >= n_packed, "nic_small_rollout_bwd_wgrad: slab rows (%lld) shorter than the packed weights (%d)",
                 (long long)slab_stride, n_packed);
-    return launch_bwd_wgrad(d, nullptr, states_hist, hidden_hist, logits_hist, g_reward, slab, slab_stride, nic::as_stream(stream),
-                            "nic_small_rollout_bwd_wgrad");
+    return launch_bwd<true>(d, nullptr, states_hist, hidden_hist, logits_hist, g_reward, nullptr, nullptr, slab, slab_stride,
+                            nic::as_stream(stream), "nic_small_rollout_bwd_wgrad");
+}
+
+/* the dz-history sweep: the referee of the in-kernel weight gradients (FusedRollout.small_wgrad_in_kernel = False) */
+int nic_small_rollout_bwd(const NicSmallRolloutDesc* d, const float* states_hist, const float* hidden_hist,
+                          const float* logits_hist, NicTable2 g_reward, float* dz_hidden, float* dz_out, void* stream) {
+    if (int e = validate(d, "nic_small_rollout_bwd")) return e;
+    NIC_REQUIRE(d->lane_scenarios != 16, "nic_small_rollout_bwd: the dz-history sweep reads the [row][t][ldb] history of the 32-scenario forward");
+    NIC_REQUIRE(states_hist && hidden_hist && logits_hist && g_reward.p && dz_hidden && dz_out,
+                "nic_small_rollout_bwd: null buffer");
+    return launch_bwd<false>(d, nullptr, states_hist, hidden_hist, logits_hist, g_reward, dz_hidden, dz_out, nullptr, 0,
+                             nic::as_stream(stream), "nic_small_rollout_bwd");
 }
 
 /* ---- K models in one launch (csrc/small_ensemble_plan.h holds the slice sizes and the checks) ---- */
 int nic_small_rollout_ensemble_slices(const NicSmallRolloutDesc* d, NicSmallEnsembleSlices* out) {
     NIC_REQUIRE(d != nullptr && out != nullptr, "nic_small_rollout_ensemble_slices: null argument");
-    NIC_REQUIRE(d->n_scenarios > 0 && d->ldb >= d->n_scenarios && d->T > 0 && d->F >= 1 && d->F <= NIC_SR_MAX_INPUTS && d->n_hidden >= 1 &&
-                    d->n_hidden <= 3 && d->n_out >= 1 && d->n_out <= NIC_SR_MAX_OUTPUTS,
-                "nic_small_rollout_ensemble_slices: bad sizes");
-    NIC_REQUIRE(d->lane_scenarios == 0 || d->lane_scenarios == 16 || d->lane_scenarios == 32,
-                "nic_small_rollout_ensemble_slices: lane_scenarios must be 0, 16 or 32");
+    const SizeFault fault = size_fault(*d);   // (sizes alone: the query takes descriptors without buffers or a chain)
+    NIC_REQUIRE((fault == SIZES_OK || fault == BAD_LANES) && d->F >= 1 && d->F <= NIC_SR_MAX_INPUTS, "nic_small_rollout_ensemble_slices: bad sizes");
+    NIC_REQUIRE(fault != BAD_LANES, "nic_small_rollout_ensemble_slices: lane_scenarios must be 0, 16 or 32");
     *out = slices_of(*d);
     return 0;
 }
@@ -619,7 +563,7 @@ int nic_small_rollout_ensemble_bwd_wgrad(const NicSmallRolloutDesc* d, const Nic
     const int why = nic::small_ensemble_check_bwd(*e, slices_of(*d), slab_row_stride);
     NIC_REQUIRE(why == 0, "nic_small_rollout_ensemble_bwd_wgrad: %s (%d models, slab rows of %lld)", nic::small_ensemble_reason(why),
                 e->n_models, (long long)slab_row_stride);
-    return launch_bwd_wgrad(d, e, states_hist, hidden_hist, logits_hist, g_reward, slab, slab_row_stride, nic::as_stream(stream),
-                            "nic_small_rollout_ensemble_bwd_wgrad");
+    return launch_bwd<true>(d, e, states_hist, hidden_hist, logits_hist, g_reward, nullptr, nullptr, slab, slab_row_stride,
+                            nic::as_stream(stream), "nic_small_rollout_ensemble_bwd_wgrad");
 }
 }

@@ -5,13 +5,20 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/nic_rollout.h"
+#include "nic_common.h"
+#include "small_rollout_variants.h"
 
 namespace nic {
 // rows ([rows][T][ldb] floats) of the state / logit history of the 16-wide kernels: a scenario's slots are padded to whole 16-byte
 // accesses (n_out = 1: one float, no padding)
 __host__ __device__ inline int sr16_state_rows(int F) { return (F + 3) & ~3; }
 __host__ __device__ inline int sr16_logit_rows(int n_out) { return n_out == 1 ? 1 : (n_out + 3) & ~3; }
-inline const char* sr_shape_name(int shape) { return shape == 1 ? "one_store" : (shape == 2 ? "serial" : "any"); }
+// records the kernel name of a launch (small_rollout_variants.h words it); e: nullptr = one model
+inline void sr_note_kernel(SrRoute route, const NicSmallRolloutDesc& d, int shape, const NicSmallEnsemble* e) {
+    char name[160];
+    sr_kernel_name(name, sizeof(name), route, sr_lane_width(d), d.n_hidden, shape, e ? e->n_models : 0);
+    note_kernelf("%s", name);
+}
 // what the ensemble instantiations of the kernels take of a NicSmallEnsemble: floats between two models' slices of the buffers
 // that kernel touches (the forward's history strides are zero when the histories are NULL: NULL + m x 0 stays NULL)
 struct SrFwdStrides { int64_t weights, rewards, final_state, states, hidden, logits; };
@@ -24,10 +31,11 @@ inline SrFwdStrides sr_fwd_strides(const NicSmallEnsemble* e, bool with_history)
 inline SrBwdStrides sr_bwd_strides(const NicSmallEnsemble* e) {
     return e ? SrBwdStrides{e->weights, e->states, e->hidden, e->logits, e->slab} : SrBwdStrides{0, 0, 0, 0, 0};
 }
-// e: nullptr = one model (the single-model instantiations), else K models, one grid row each (nic_small_rollout_ensemble_*)
-void small_rollout16_fwd(const NicSmallRolloutDesc& d, int shape, float* rewards, float* state_final, float* states_hist,
+// e: nullptr = one model (the single-model instantiations), else K models, one grid row each (nic_small_rollout_ensemble_*);
+// false: no kernel for this n_hidden, nothing was launched
+bool small_rollout16_fwd(const NicSmallRolloutDesc& d, int shape, float* rewards, float* state_final, float* states_hist,
                          float* hidden_hist, float* logits_hist, hipStream_t s, const NicSmallEnsemble* e = nullptr);
-void small_rollout16_bwd_wgrad(const NicSmallRolloutDesc& d, int shape, const float* states_hist, const float* hidden_hist,
+bool small_rollout16_bwd_wgrad(const NicSmallRolloutDesc& d, int shape, const float* states_hist, const float* hidden_hist,
                                const float* logits_hist, NicTable2 g_reward, float* slab, int64_t slab_stride, hipStream_t s,
                                const NicSmallEnsemble* e = nullptr);
 }  // namespace nic

@@ -29,6 +29,7 @@
 #include "nic_common.h"
 #include "small_rollout16.h"
 #include "small_rollout_body.h"
+#include "small_rollout_mfma.h"
 
 namespace {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -45,7 +46,6 @@ __device__ unsigned long long* g_sr16_stamps = nullptr;
 #else
 #define SR_STAMP(t, point) do { } while (0)
 #endif
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ int row16(int e, int g) { return 16 * (e >> 2) + 4 * g + (e & 3); }
 __device__ __forceinline__ float sel4(int g, float a, float b, float c, float d) {
@@ -53,33 +53,11 @@ __device__ __forceinline__ float sel4(int g, float a, float b, float c, float d)
     return (g & 2) ? hi : lo;
 }
 
-// ELU of 8 activations: the packed-FMA series of small_rollout.hip's elu16 (same values as nic::elu1)
+// ELU of 8 activations (same values as nic::elu1)
 __device__ __forceinline__ void elu8(const f32x4& z0, const f32x4& z1, float (&out)[8]) {
     const float z[8] = {z0[0], z0[1], z0[2], z0[3], z1[0], z1[1], z1[2], z1[3]};
 #pragma unroll
-    for (int r = 0; r < 8; r += 2) {
-        const f32x2 x = {z[r], z[r + 1]};
-        f32x2 p = __builtin_elementwise_fma(x, (f32x2)(1.f / 720.f), (f32x2)(1.f / 120.f));
-        p = __builtin_elementwise_fma(x, p, (f32x2)(1.f / 24.f));
-        p = __builtin_elementwise_fma(x, p, (f32x2)(1.f / 6.f));
-        p = __builtin_elementwise_fma(x, p, (f32x2)(0.5f));
-        p = __builtin_elementwise_fma(x, p, (f32x2)(1.f));
-        const f32x2 sp = x * p;
-        const float e0 = __expf(x.x) - 1.f, e1 = __expf(x.y) - 1.f;
-        const float n0 = x.x > -0.35f ? sp.x : e0, n1 = x.y > -0.35f ? sp.y : e1;
-        out[r] = x.x > 0.f ? x.x : n0;
-        out[r + 1] = x.y > 0.f ? x.y : n1;
-    }
-}
-
-template <int SHAPE>
-__device__ __forceinline__ void fix_shape16(NicSmallRolloutDesc& d, int n_hidden) {
-    d.n_hidden = n_hidden;
-    if (SHAPE == 1) {
-        d.Ws = 4; d.Ww = 0; d.We = 0; d.Wn = 0; d.E = 0; d.head = 0; d.F = 4; d.n_out = 1;
-    } else if (SHAPE == 2) {
-        d.Ws = 4; d.Ww = 3; d.We = 4; d.Wn = 1; d.E = 2; d.head = 1; d.F = 15; d.n_out = 4;
-    }
+    for (int r = 0; r < 8; r += 2) nic::sr_elu_pair(z[r], z[r + 1], out[r], out[r + 1]);
 }
 
 // one 32-wide layer on resident fragments: acc[tile] = bias + sum over the 8 steps of A[tile][e] * x[e]
@@ -121,7 +99,7 @@ __global__ __launch_bounds__(64, 2) void small_rollout16_fwd_kernel(NicSmallRoll
     d.weights = weights;
     d.demand = demand;
     d.state0 = state0;
-    fix_shape16<SHAPE>(d, NL);
+    sr_fix_shape<SHAPE>(d, NL);
 
     // ---- weight fragments, resident for the whole horizon (A row m = j of each 16-row tile)
     float aW1[2][4], cB[NL + 1][8];
@@ -266,7 +244,7 @@ __global__ __launch_bounds__(64, 2) void small_rollout16_bwd_kernel(NicSmallRoll
     const int64_t ldb = d.ldb, tl = (int64_t)d.T * ldb;
     d.weights = weights;
     d.demand = demand;
-    fix_shape16<SHAPE>(d, NL);
+    sr_fix_shape<SHAPE>(d, NL);
 
     // transposed weight fragments: A row m = j of tile ot is INPUT feature 16 ot + j of the layer being back-propagated through
     float aWoT[2][2], aWhT[NH][2][8], aW1T[8];
@@ -529,47 +507,27 @@ extern "C" int nic_tuning_set_small_rollout_stamps(void* buf) {   // buf: device
 namespace nic {
 
 // e == nullptr: the single-model kernels (grid y = 1, no strides); else the ensemble instantiations, one grid row per model
-void small_rollout16_fwd(const NicSmallRolloutDesc& d, int shape, float* rewards, float* state_final, float* states_hist,
+bool small_rollout16_fwd(const NicSmallRolloutDesc& d, int shape, float* rewards, float* state_final, float* states_hist,
                          float* hidden_hist, float* logits_hist, hipStream_t s, const NicSmallEnsemble* e) {
-    if (e) nic::note_kernelf("small_rollout16_fwd_kernel<%d,%s,models=%d>", d.n_hidden, nic::sr_shape_name(shape), e->n_models);
-    else nic::note_kernelf("small_rollout16_fwd_kernel<%d,%s>", d.n_hidden, nic::sr_shape_name(shape));
     const dim3 grid(nic::ceil_div(d.n_scenarios, 16), e ? e->n_models : 1), block(64);
     const nic::SrFwdStrides es = nic::sr_fwd_strides(e, states_hist != nullptr);   // (the kernels add m x stride unconditionally)
-#define NIC_SR16_FWD_(NL, SH, ENS)                                                                                              \
-    hipLaunchKernelGGL((small_rollout16_fwd_kernel<NL, SH, ENS>), grid, block, 0, s, d, d.weights, d.demand, d.state0, rewards, \
-                       state_final, states_hist, hidden_hist, logits_hist, es)
-#define NIC_SR16_FWD(NL, SH) do { if (e) NIC_SR16_FWD_(NL, SH, true); else NIC_SR16_FWD_(NL, SH, false); } while (0)
-    if (shape == 1 && d.n_hidden == 3) NIC_SR16_FWD(3, 1);
-    else if (shape == 1 && d.n_hidden == 2) NIC_SR16_FWD(2, 1);
-    else if (shape == 2 && d.n_hidden == 2) NIC_SR16_FWD(2, 2);
-    else if (shape == 2 && d.n_hidden == 3) NIC_SR16_FWD(3, 2);
-    else if (d.n_hidden == 1) NIC_SR16_FWD(1, 0);
-    else if (d.n_hidden == 2) NIC_SR16_FWD(2, 0);
-    else NIC_SR16_FWD(3, 0);
-#undef NIC_SR16_FWD
-#undef NIC_SR16_FWD_
+    sr_note_kernel(SR_FWD, d, shape, e);
+    return sr_dispatch<SR_FWD>(sr_variant(SR_FWD, shape, d.n_hidden), e != nullptr, [&](auto nl, auto sh, auto ens) {
+        hipLaunchKernelGGL((small_rollout16_fwd_kernel<nl(), sh(), ens()>), grid, block, 0, s, d, d.weights, d.demand, d.state0, rewards,
+                           state_final, states_hist, hidden_hist, logits_hist, es);
+    });
 }
 
-void small_rollout16_bwd_wgrad(const NicSmallRolloutDesc& d, int shape, const float* states_hist, const float* hidden_hist,
+bool small_rollout16_bwd_wgrad(const NicSmallRolloutDesc& d, int shape, const float* states_hist, const float* hidden_hist,
                                const float* logits_hist, NicTable2 g_reward, float* slab, int64_t slab_stride, hipStream_t s,
                                const NicSmallEnsemble* e) {
-    if (e) nic::note_kernelf("small_rollout16_bwd_kernel<%d,wgrad,%s,models=%d>", d.n_hidden, nic::sr_shape_name(shape), e->n_models);
-    else nic::note_kernelf("small_rollout16_bwd_kernel<%d,wgrad,%s>", d.n_hidden, nic::sr_shape_name(shape));
     const dim3 grid(nic::ceil_div(d.n_scenarios, 16), e ? e->n_models : 1), block(64);
     const nic::SrBwdStrides es = nic::sr_bwd_strides(e);
-#define NIC_SR16_BWD_(NL, SH, ENS)                                                                                                     \
-    hipLaunchKernelGGL((small_rollout16_bwd_kernel<NL, SH, ENS>), grid, block, 0, s, d, d.weights, d.demand, states_hist, hidden_hist, \
-                       logits_hist, g_reward, slab, slab_stride, es)
-#define NIC_SR16_BWD(NL, SH) do { if (e) NIC_SR16_BWD_(NL, SH, true); else NIC_SR16_BWD_(NL, SH, false); } while (0)
-    if (shape == 1 && d.n_hidden == 3) NIC_SR16_BWD(3, 1);
-    else if (shape == 1 && d.n_hidden == 2) NIC_SR16_BWD(2, 1);
-    else if (shape == 2 && d.n_hidden == 2) NIC_SR16_BWD(2, 2);
-    else if (shape == 2 && d.n_hidden == 3) NIC_SR16_BWD(3, 2);
-    else if (d.n_hidden == 1) NIC_SR16_BWD(1, 0);
-    else if (d.n_hidden == 2) NIC_SR16_BWD(2, 0);
-    else NIC_SR16_BWD(3, 0);
-#undef NIC_SR16_BWD
-#undef NIC_SR16_BWD_
+    sr_note_kernel(SR_BWD_WGRAD, d, shape, e);
+    return sr_dispatch<SR_BWD_WGRAD>(sr_variant(SR_BWD_WGRAD, shape, d.n_hidden), e != nullptr, [&](auto nl, auto sh, auto ens) {
+        hipLaunchKernelGGL((small_rollout16_bwd_kernel<nl(), sh(), ens()>), grid, block, 0, s, d, d.weights, d.demand, states_hist,
+                           hidden_hist, logits_hist, g_reward, slab, slab_stride, es);
+    });
 }
 
 }  // namespace nic

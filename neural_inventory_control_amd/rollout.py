@@ -746,22 +746,10 @@ class FusedRollout:
         cache[slot] = (src, key)
 
     def _set_g_reward(self, B, grad_scale):
-        """g_reward[b] = d loss / d reward[b, t] for the live scenarios, 0 in the padding columns.  Two launches that a training
-        loop repeats with the same numbers every step: skipped while the buffer, the batch size and the (host-side) scale are the
-        ones of the previous call - the whole-horizon routes' steps are a handful of launches, these were two of them."""
-        key = (self.g_reward.data_ptr(), B, grad_scale) if isinstance(grad_scale, (int, float)) else None
-        if key is not None and key == getattr(self, "_g_reward_key", None):
-            return
-        self.g_reward.zero_()
-        self.g_reward[:B] = grad_scale
-        self._g_reward_key = key
+        self._g_reward_key = sr.set_g_reward(self.g_reward, B, grad_scale, getattr(self, "_g_reward_key", None))
 
     def _assign_grads(self, accumulate):
-        for p, g in self.param_grads():
-            if accumulate and p.grad is not None and p.grad is not g:
-                p.grad.add_(g)
-            else:
-                p.grad = g
+        sr.assign_grads(self.param_grads(), accumulate)
 
     def _problem_for(self, data):
         """EnvProblem of a batch (cached per presented tensors, see layout.ProblemCache)."""
@@ -779,14 +767,9 @@ class FusedRollout:
         if prob.E:
             self._copy_if_changed("s0_ech", s0.ech[:, :, :B], data["initial_echelon_inventories"])
         ub = self._ub() if self.head != "softplus" else 0.0
-        # Scenarios per wavefront.  Training: 16 (v_mfma_f32_16x16x4_f32, wave-native activation history) - measured against 32:
-        # cfg1 0.55 -> 0.30 ms, cfg4 (16,384 scenarios: 32 leaves half the SIMDs without a wavefront) 0.83 -> 0.70 ms, cfg2
-        # (32,768) 1.16 -> 1.07 ms, 65,536 scenarios 2.28 -> 1.87 ms.  Evaluation (no history): 16 while 32 would leave SIMDs
-        # idle, else 32 (the per-lane head / env-step code is replicated in four lane groups instead of two).  The dz-history
-        # sweep (small_wgrad_in_kernel = False) only exists in the 32-wide form.
-        width = self.small_lane_scenarios or (16 if (train or B <= 16384) else 32)
+        width = sr.lane_width(self.small_lane_scenarios, train, B)
         if train and not self.small_wgrad_in_kernel:
-            width = 32
+            width = 32   # (the dz-history sweep only exists in the 32-wide form)
         desc = plan.desc(T, shift, self.sr_weights, demand_soa, self.sr_state0, ub, round_orders=self._round, prob=prob,
                          lane_scenarios=width)
         hist = (self.sr_states, self.sr_hidden, self.sr_logits) if train else (None, None, None)
@@ -802,12 +785,10 @@ class FusedRollout:
         self._set_g_reward(B, grad_scale)
         if self.small_wgrad_in_kernel:
             self._k("small_rollout_bwd", sr.small_rollout_bwd_wgrad, desc, *hist, Table(self.g_reward, 0, 1), self.sr_slab)
-            # one partial gradient per wavefront: only the rows THIS width's launch wrote are summed (the slab is sized for the
-            # 16-wide form; a 32-wide launch fills half of it and must not pick up an earlier 16-wide run's rows)
-            # ... and the step's two sums - partial gradients over the wavefronts, costs over (period, scenario) - in two small
-            # launches with a fixed order (csrc/small_reduce.hip).  As torch reductions these were four launches, 37-46 us of a
-            # 1-ms step (the row sums end in a semaphore pass with its own memset).
-            n_rows = (B + width - 1) // width
+            # the step's two sums - partial gradients over the wavefronts, costs over (period, scenario) - in two small launches
+            # with a fixed order (csrc/small_reduce.hip).  As torch reductions these were four launches, 37-46 us of a 1-ms step
+            # (the row sums end in a semaphore pass with its own memset).
+            n_rows = sr.slab_rows_written(B, width)
             need = sr.small_rollout_reduce_scratch(n_rows, self.sr_grad.numel(), self.rewards.numel())
             if getattr(self, "sr_scratch", None) is None or self.sr_scratch.numel() < need:
                 self.sr_scratch, self.sr_totals = torch.empty(need, device=self.device), torch.zeros(2, device=self.device)

@@ -80,7 +80,7 @@ class SmallPolicyEnsemble:
         # (one single-model engine per model: problem cache, LazyLinear materialisation and the upper bound are theirs; they
         # allocate nothing until they run)
         self._engines = [FusedRollout(m, problem_params, device) for m in self.models]
-        self.small_lane_scenarios = 0   # 16 or 32 scenarios per wavefront (0: FusedRollout's rule)
+        self.small_lane_scenarios = 0   # 16 or 32 scenarios per wavefront (0: small_rollout.lane_width's rule)
         self.last_kernels = {}          # launch class -> kernel name the library recorded in the last run
         self.plan = None
         self.states = None
@@ -151,7 +151,7 @@ class SmallPolicyEnsemble:
     def run(self, data, periods, ignore_periods=0, train=True, observation_params=None, demand_soa=None, grad_scale=None,
             accumulate_grads=False, discrete_allocation=False):
         """Rollout of one batch under every model (and, if `train`, d(mean loss)/d(theta) into every model's `param.grad`: views
-        into one [K][P] gradient buffer, `accumulate_grads` adds - `FusedRollout._assign_grads`'s rules).  Arguments as
+        into one [K][P] gradient buffer, `accumulate_grads` adds - `small_rollout.assign_grads`).  Arguments as
         `FusedRollout.run`.  Returns (total [K], reported [K]) device tensors; `rewards` [K][T][ldb] holds the per-period costs."""
         if discrete_allocation and train:
             raise ValueError("discrete_allocation is an evaluation-time option of the fused rollout")
@@ -174,7 +174,7 @@ class SmallPolicyEnsemble:
                 self.state0[b:b + prob.E * prob.We].view(prob.E, prob.We, -1)[:, :, :B].copy_(
                     data["initial_echelon_inventories"].permute(1, 2, 0))
         ub = lead._ub() if self.head != "softplus" else 0.0
-        width = self.small_lane_scenarios or (16 if (train or B <= 16384) else 32)   # (FusedRollout._run_small's rule)
+        width = sr.lane_width(self.small_lane_scenarios, train, B)
         desc = self.plan.desc(T, shift, self.weights, demand_soa, self.state0, ub, round_orders=discrete_allocation, prob=prob,
                               lane_scenarios=width)
         hist = (self.states, self.hidden, self.logits) if train else (None, None, None)
@@ -184,16 +184,11 @@ class SmallPolicyEnsemble:
         if train:
             if grad_scale is None:
                 grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
-            gkey = (B, grad_scale) if isinstance(grad_scale, (int, float)) else None
-            if gkey is None or gkey != self._g_reward_key:
-                self.g_reward.zero_()
-                self.g_reward[:B] = grad_scale
-                self._g_reward_key = gkey
+            self._g_reward_key = sr.set_g_reward(self.g_reward, B, grad_scale, self._g_reward_key)
             row = self.slab.shape[2]
             sr.small_rollout_ensemble_bwd_wgrad(desc, self.ens, *hist, Table(self.g_reward, 0, 1), self.slab, row)
             self._note("bwd")
-            # (only the rows THIS width's launch wrote are summed, as in FusedRollout._run_small)
-            sr.small_rollout_ensemble_reduce(self.ens, self.slab, (B + width - 1) // width, row, self.grad.shape[1], self.grad,
+            sr.small_rollout_ensemble_reduce(self.ens, self.slab, sr.slab_rows_written(B, width), row, self.grad.shape[1], self.grad,
                                              self.rewards, n_el, ignore_periods * ld, self.totals, self.scratch)
         else:   # the same reduction, costs only: an evaluation pass returns the very bits a training pass does
             sr.small_rollout_ensemble_reduce(self.ens, None, 0, 0, 0, None, self.rewards, n_el, ignore_periods * ld, self.totals,
@@ -201,9 +196,5 @@ class SmallPolicyEnsemble:
         self._note("reduce")
         tt = self.totals.clone()   # (the caller's tensors must not change under a later step)
         if train:
-            for p, g in self.param_grads():
-                if accumulate_grads and p.grad is not None and p.grad is not g:
-                    p.grad.add_(g)
-                else:
-                    p.grad = g
+            sr.assign_grads(self.param_grads(), accumulate_grads)
         return tt[:, 0], tt[:, 1]

@@ -1,7 +1,12 @@
-"""Whole-horizon rollout of the small (32-wide, one-store chain) policies through `nic_small_rollout_fwd/bwd`
-(csrc/small_rollout.hip): ONE kernel runs all T periods of `Trainer.simulate_batch` (trainer.py:190-213), one lane per
-scenario with pipelines and activations in registers; the backward sweep is a second kernel plus one weight-gradient GEMM
-per layer contracting over (period x scenario).  Used by `FusedRollout` when `SmallRollout.supports(...)`.
+"""Whole-horizon rollout of the small (32-wide, one-store chain) policies through `nic_small_rollout_*` (csrc/small_rollout.hip:
+32 scenarios per wavefront, csrc/small_rollout16.hip: 16): ONE kernel runs all T periods of `Trainer.simulate_batch`
+(trainer.py:190-213) with the layers on the matrix cores, the weights resident in registers and the per-scenario state, head and env
+step per lane; a second kernel sweeps the horizon backwards and contracts the weight gradients itself (one partial gradient per
+wavefront), and `nic_small_rollout_reduce` sums those and the costs.  `nic_small_rollout_bwd`, the backward sweep that writes a dz
+history for one weight-gradient GEMM per layer, is kept as the referee of the in-kernel gradients.  Which kernel instantiation a
+request runs is decided in csrc/small_rollout_variants.h.  Used by `FusedRollout` when `SmallRolloutPlan.supports(...)` and by
+`SmallPolicyEnsemble`; the rules both engines follow around the launches (`lane_width`, `slab_rows_written`, `set_g_reward`,
+`assign_grads`) are here.
 
 Descriptor building is pointer plumbing and device-agnostic (the CPU test build of the kernel bodies uses it too).
 """
@@ -74,7 +79,7 @@ class SmallRolloutPlan:
         d.detach_input = int(self.head == "serial")
         d.round_orders = int(bool(round_orders))
         d.upper_bound = float(upper_bound)
-        d.lane_scenarios = int(lane_scenarios)   # 0: the library picks 16 or 32 scenarios per wavefront from the batch size
+        d.lane_scenarios = int(lane_scenarios)   # 16 or 32 scenarios per wavefront; 0 means 32 (the engines choose with `lane_width`)
         d.weights, d.demand, d.state0 = weights.data_ptr(), demand_soa.data_ptr(), state0.data_ptr()
         d.underage, d.holding = p.underage.t2(), p.holding.t2()
         lead = p.lead  # (s, w, b) table with one store and one supplier column
@@ -83,6 +88,41 @@ class SmallRolloutPlan:
         d.ech_holding, d.ech_lead = p.ech_holding.t2(), p.ech_lead.t2()
         self._keep = (weights, demand_soa, state0, p)
         return d
+
+
+def lane_width(requested, train, B):
+    """Scenarios per wavefront of a run: `requested` (16 or 32) if set.  Training: 16 (v_mfma_f32_16x16x4_f32, wave-native
+    activation history) - measured against 32: cfg1 0.55 -> 0.30 ms, cfg4 (16,384 scenarios: 32 leaves half the SIMDs without a
+    wavefront) 0.83 -> 0.70 ms, cfg2 (32,768) 1.16 -> 1.07 ms, 65,536 scenarios 2.28 -> 1.87 ms.  Evaluation (no history): 16
+    while 32 would leave SIMDs idle, else 32 (the per-lane head / env-step code is replicated in four lane groups instead of two)."""
+    return requested or (16 if (train or B <= 16384) else 32)
+
+
+def slab_rows_written(B, width):
+    """Rows of the partial-gradient slab a backward launch of this width wrote: one per wavefront.  The slab is sized for the 16-wide
+    form; a 32-wide launch fills half of it, and the reduction must not pick up an earlier 16-wide run's rows."""
+    return (B + width - 1) // width
+
+
+def set_g_reward(g_reward, B, grad_scale, last_key):
+    """g_reward[b] = d loss / d reward[b, t] for the live scenarios, 0 in the padding columns.  Two launches that a training loop
+    repeats with the same numbers every step: skipped while the buffer, the batch size and the (host-side) scale are those of
+    `last_key`, the key the previous call returned (None: fill).  Returns the key of this call."""
+    key = (g_reward.data_ptr(), B, grad_scale) if isinstance(grad_scale, (int, float)) else None
+    if key is None or key != last_key:
+        g_reward.zero_()
+        g_reward[:B] = grad_scale
+    return key
+
+
+def assign_grads(param_grads, accumulate):
+    """param.grad <- the engine's gradient buffer; `accumulate` adds to a gradient that is already there (unless that IS the
+    engine's buffer from an earlier run, which this run has overwritten)."""
+    for p, g in param_grads:
+        if accumulate and p.grad is not None and p.grad is not g:
+            p.grad.add_(g)
+        else:
+            p.grad = g
 
 
 def small_rollout_fwd(desc, rewards, state_final, states_hist, hidden_hist, logits_hist):

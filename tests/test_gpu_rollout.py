@@ -864,6 +864,84 @@ def test_small_route_run_time_structure_kernels_match_the_per_period_route(varia
         torch.testing.assert_close(a[3][k], b[3][k], **STATE_TOL)
 
 
+# What the whole-horizon route records for the two compiled-in chains (cfg2: one store, cfg4: serial) at every depth, literally:
+# (workload, hidden layers, mode) -> (small_rollout_fwd, small_rollout_bwd); modes: in-kernel weight gradients at 16 and at 32 scenarios
+# per wavefront, and the dz-history backward (32 only).  A name states the request; which instantiation runs it is
+# csrc/small_rollout_variants.h's decision (tests/test_small_rollout_variants_host.py), and a wrong one shows in the numbers below.
+SMALL_DISPATCH_KERNELS = {
+    ("cfg2", 1, "wgrad16"): ("small_rollout16_fwd_kernel<1,one_store>", "small_rollout16_bwd_kernel<1,wgrad,one_store>"),
+    ("cfg2", 1, "wgrad32"): ("small_rollout_fwd_mfma_kernel<1,one_store>", "small_rollout_bwd_mfma_kernel<1,wgrad,one_store>"),
+    ("cfg2", 1, "dz32"): ("small_rollout_fwd_mfma_kernel<1,one_store>", "small_rollout_bwd_mfma_kernel<1,one_store>"),
+    ("cfg2", 2, "wgrad16"): ("small_rollout16_fwd_kernel<2,one_store>", "small_rollout16_bwd_kernel<2,wgrad,one_store>"),
+    ("cfg2", 2, "wgrad32"): ("small_rollout_fwd_mfma_kernel<2,one_store>", "small_rollout_bwd_mfma_kernel<2,wgrad,one_store>"),
+    ("cfg2", 2, "dz32"): ("small_rollout_fwd_mfma_kernel<2,one_store>", "small_rollout_bwd_mfma_kernel<2,one_store>"),
+    ("cfg2", 3, "wgrad16"): ("small_rollout16_fwd_kernel<3,one_store>", "small_rollout16_bwd_kernel<3,wgrad,one_store>"),
+    ("cfg2", 3, "wgrad32"): ("small_rollout_fwd_mfma_kernel<3,one_store>", "small_rollout_bwd_mfma_kernel<3,wgrad,one_store>"),
+    ("cfg2", 3, "dz32"): ("small_rollout_fwd_mfma_kernel<3,one_store>", "small_rollout_bwd_mfma_kernel<3,one_store>"),
+    ("cfg4", 1, "wgrad16"): ("small_rollout16_fwd_kernel<1,serial>", "small_rollout16_bwd_kernel<1,wgrad,serial>"),
+    ("cfg4", 1, "wgrad32"): ("small_rollout_fwd_mfma_kernel<1,serial>", "small_rollout_bwd_mfma_kernel<1,wgrad,serial>"),
+    ("cfg4", 1, "dz32"): ("small_rollout_fwd_mfma_kernel<1,serial>", "small_rollout_bwd_mfma_kernel<1,serial>"),
+    ("cfg4", 2, "wgrad16"): ("small_rollout16_fwd_kernel<2,serial>", "small_rollout16_bwd_kernel<2,wgrad,serial>"),
+    ("cfg4", 2, "wgrad32"): ("small_rollout_fwd_mfma_kernel<2,serial>", "small_rollout_bwd_mfma_kernel<2,wgrad,serial>"),
+    ("cfg4", 2, "dz32"): ("small_rollout_fwd_mfma_kernel<2,serial>", "small_rollout_bwd_mfma_kernel<2,serial>"),
+    ("cfg4", 3, "wgrad16"): ("small_rollout16_fwd_kernel<3,serial>", "small_rollout16_bwd_kernel<3,wgrad,serial>"),
+    ("cfg4", 3, "wgrad32"): ("small_rollout_fwd_mfma_kernel<3,serial>", "small_rollout_bwd_mfma_kernel<3,wgrad,serial>"),
+    ("cfg4", 3, "dz32"): ("small_rollout_fwd_mfma_kernel<3,serial>", "small_rollout_bwd_mfma_kernel<3,serial>"),
+}
+
+
+@pytest.mark.parametrize("n_hidden", [1, 2, 3])
+@pytest.mark.parametrize("workload", ["cfg2", "cfg4"])
+def test_small_route_dispatch_cells_match_the_per_period_route(workload, n_hidden):
+    """Every (chain, depth) cell of the whole-horizon kernels' dispatch through the engine, in the three modes that reach different
+    kernels, against the engine's own per-period route: recorded kernel names, costs, gradients, final state.  40 scenarios (three
+    16-scenario wavefronts or two 32-scenario ones, the last ragged), 5 periods."""
+    from collections import defaultdict
+    import copy
+    from neural_inventory_control_amd import workloads
+    from neural_inventory_control_amd.rollout import KernelTimer
+    setting, policy, _, _, _ = workloads.get(workload)
+    policy = copy.deepcopy(policy)
+    policy["neurons_per_hidden_layer"]["master"] = [32] * n_hidden
+    obs = defaultdict(lambda: None, setting["observation_params"])
+    n, T = 40, 5
+    sc = Scenario(T, setting["problem_params"], setting["store_params"], setting["warehouse_params"], setting["echelon_params"],
+                  n, obs, setting["seeds"])
+    data = {k: v.to(DEV) for k, v in sc.get_data().items()}
+    F = data["initial_inventories"].shape[1] * data["initial_inventories"].shape[2]
+    if policy["name"] != "vanilla_one_store":
+        F += sum(int(np.prod(data[k].shape[1:])) for k in ("initial_warehouse_inventories", "initial_echelon_inventories")
+                 if k in data)
+
+    def run(mode):
+        torch.manual_seed(9)
+        model = NeuralNetworkCreator().create_neural_network(sc, policy, device=DEV)
+        eng = FusedRollout(model, setting["problem_params"], DEV)
+        eng.use_small = mode != "periods"
+        if mode != "periods":
+            eng.small_wgrad_in_kernel = mode != "dz32"
+            eng.small_lane_scenarios = 16 if mode == "wgrad16" else 32
+        eng.materialize(F)
+        eng.timer = KernelTimer()   # (records which kernel the C ABI launched for every class of the step)
+        total, rep = eng.run(data, T, 2, train=True, observation_params=obs)
+        torch.cuda.synchronize()
+        assert (eng.small is not None) == (mode != "periods")
+        assert len(eng._linears()) == n_hidden + 1
+        names = (eng.timer.names.get("small_rollout_fwd"), eng.timer.names.get("small_rollout_bwd"))
+        return (float(total), float(rep), [p.grad.clone() for p in model.parameters()],
+                {k: v.clone() for k, v in eng.final_state().items()}), names
+    b, names = run("periods")
+    assert names == (None, None)
+    for mode in ("wgrad16", "wgrad32", "dz32"):
+        a, names = run(mode)
+        assert names == SMALL_DISPATCH_KERNELS[workload, n_hidden, mode], mode
+        assert abs(a[0] - b[0]) <= 2e-6 * abs(b[0]) and abs(a[1] - b[1]) <= 2e-6 * abs(b[1]), mode
+        for x, y in zip(a[2], b[2]):
+            assert float((x - y).norm() / (y.norm() + 1e-30)) < GRAD_TOL, mode
+        for k in b[3]:
+            torch.testing.assert_close(a[3][k], b[3][k], **STATE_TOL)
+
+
 @pytest.mark.parametrize("name", ["cfg2_one_store_backlogged_vanilla", "cfg4_serial_vanilla"])
 def test_small_route_equals_per_period_route(name):
     """FusedRollout takes the whole-horizon route for these policies; it must agree with its own per-period route."""

@@ -75,15 +75,14 @@ def _golden_setting(name):
 
 @functools.lru_cache(maxsize=None)
 def _synthetic_data(chain, B, T):
-    """chains that take the run-time-structure instantiations (SHAPE 0): one store with a 3-slot pipeline; store + warehouse + ONE echelon"""
+    """chains that take the run-time-structure instantiations (SHAPE 0): one store with a 3-slot pipeline; store + warehouse + ONE
+    echelon - and the two chains that are compiled in, as the workloads have them: "one_store" (cfg2), "serial" (cfg4)"""
+    setting, policy, _, _, _ = workloads.get("cfg2" if chain.startswith("one_store") else "cfg4")
+    setting = copy.deepcopy(setting)
     if chain == "one_store_ws3":
-        setting, policy, _, _, _ = workloads.get("cfg2")
-        setting = copy.deepcopy(setting)
         setting["store_params"]["lead_time"] = {"sample_across_stores": False, "vary_across_samples": False, "expand": True, "value": 3}
         setting["store_params"]["initial_inventory"]["inventory_periods"] = 3
-    else:
-        setting, policy, _, _, _ = workloads.get("cfg4")
-        setting = copy.deepcopy(setting)
+    elif chain == "serial_one_echelon":
         setting["problem_params"]["n_extra_echelons"] = 1
         setting["echelon_params"] = {"holding_cost": [0.1], "lead_time": [3]}
     obs = defaultdict(lambda: None, setting["observation_params"])
@@ -96,12 +95,12 @@ def _synthetic_data(chain, B, T):
 def _synthetic_setting(chain, n_hidden, B, T):
     setting, data = _synthetic_data(chain, B, T)
     prob = EnvProblem(setting["problem_params"], data, DEV)
-    if chain == "one_store_ws3":
+    if chain.startswith("one_store"):
         head, F, n_out = "softplus", prob.Ws, 1
-        assert (prob.Ws, prob.Wn, prob.E) == (3, 0, 0)
+        assert (prob.Ws, prob.Wn, prob.E) == (3 if chain == "one_store_ws3" else 4, 0, 0)
     else:
-        head, F, n_out = "serial", prob.Ws + prob.Ww + prob.We, 3
-        assert (prob.Wn, prob.E) == (1, 1)
+        head, F, n_out = "serial", prob.Ws + prob.Ww + prob.E * prob.We, prob.E + 2
+        assert (prob.Wn, prob.E) == (1, 1 if chain == "serial_one_echelon" else 2)
     dims = [F] + [32] * n_hidden + [n_out]
     assert sr.SmallRolloutPlan.supports(prob, head, dims)
     return _Setting(prob, head, dims, data, T, 37.0, setting["problem_params"]["n_stores"])
@@ -189,11 +188,14 @@ def _run_single(s, packed_row, width, sl, row, train=True, round_orders=False):
     return buf
 
 
-def _compare_with_single_launches(s, packed, width, train=True, round_orders=False):
+def _compare_with_single_launches(s, packed, width, train=True, round_orders=False, kernels=None):
+    """kernels: {"fwd": ..., "bwd": ...} the recorded names the launches must have (None: only their `models=K`)"""
     K, B = packed.shape[0], s.prob.B
     buf, sl, st, row, names = _run_ensemble(s, packed, width, train, round_orders)
     for tag, name in names.items():
         assert f"models={K}" in name, (tag, name)
+    if kernels is not None:
+        assert {tag: names[tag] for tag in kernels} == kernels
     assert ("small_rollout16" in names["fwd"]) == (width == 16)
     size = dict(sl, slab=sl["slab_rows"] * row, grad=s.P0, scratch=0)
     keys = ("rewards", "final_state") + (("states", "hidden", "logits", "slab", "grad") if train else ())
@@ -242,6 +244,26 @@ def test_ensemble_launches_equal_single_launches_on_run_time_structure_chains(ch
     for T, K in ((1, 2), (7, 5), (1, 5), (7, 2)):
         s = _synthetic_setting(chain, n_hidden, B, T)
         _compare_with_single_launches(s, _random_packed(s, K, 1000 * T + K), width)
+
+
+# the compiled-in chains at the depths the fixtures lack (cfg2's policy has three hidden layers, cfg4's two): recorded names, literally
+COMPILED_IN_KERNELS = {
+    ("one_store", 2, 16): {"fwd": "small_rollout16_fwd_kernel<2,one_store,models=3>", "bwd": "small_rollout16_bwd_kernel<2,wgrad,one_store,models=3>"},
+    ("one_store", 2, 32): {"fwd": "small_rollout_fwd_mfma_kernel<2,one_store,models=3>",
+                           "bwd": "small_rollout_bwd_mfma_kernel<2,wgrad,one_store,models=3>"},
+    ("serial", 3, 16): {"fwd": "small_rollout16_fwd_kernel<3,serial,models=3>", "bwd": "small_rollout16_bwd_kernel<3,wgrad,serial,models=3>"},
+    ("serial", 3, 32): {"fwd": "small_rollout_fwd_mfma_kernel<3,serial,models=3>", "bwd": "small_rollout_bwd_mfma_kernel<3,wgrad,serial,models=3>"},
+}
+
+
+@pytest.mark.parametrize("chain,n_hidden,width", sorted(COMPILED_IN_KERNELS))
+def test_ensemble_launches_equal_single_launches_on_the_compiled_in_chains_at_the_other_depths(chain, n_hidden, width):
+    """<2,one_store> and <3,serial>: 40 scenarios (three 16-scenario wavefronts or two 32-scenario ones, the last ragged), 5 periods"""
+    s = _synthetic_setting(chain, n_hidden, 40, 5)
+    assert tuple(s.dims) == ((4, 32, 32, 1) if chain == "one_store" else (15, 32, 32, 32, 4))
+    kernels = COMPILED_IN_KERNELS[chain, n_hidden, width]
+    assert all(k.endswith(",models=3>") for k in kernels.values())
+    _compare_with_single_launches(s, _random_packed(s, 3, 77), width, kernels=kernels)
 
 
 @pytest.mark.parametrize("width", [16, 32])

@@ -51,6 +51,7 @@ def _slices(harness, shape, width):
 
 def test_build_hashes_the_plan_header():
     assert "small_ensemble_plan.h" in build.HEADERS
+    assert "small_rollout_variants.h" in build.HEADERS and "small_rollout_mfma.h" in build.HEADERS
 
 
 @pytest.mark.parametrize("shape", SHAPES)
