@@ -26,6 +26,7 @@
 #include "nic_common.h"
 #include "nic_bf16.h"
 #include "wgrad_plan.h"
+#include "wx_plan.h"
 
 namespace {
 
@@ -340,15 +341,10 @@ bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 
 
 template <int EPI>
 int launch_wx(const WxParams& p, hipStream_t s) {
-    const int64_t tiles128 = (int64_t)((p.M + 127) / 128) * ((p.ncols + 127) / 128);
-    if (tiles128 >= 2 * nic::cu_count()) {   // big launches: 128 x 128 tiles (wave tile 64 x 64)
-        nic::note_kernelf("bf16_wx_kernel<2,2,%d>", EPI);
-        hipLaunchKernelGGL((bf16_wx_kernel<2, 2, EPI>), dim3((unsigned)tiles128), dim3(kThreads), 0, s, p);
-    } else {   // smaller launches: 64 x 64 tiles, four times the workgroups
-        const int64_t tiles = (int64_t)((p.M + 63) / 64) * ((p.ncols + 63) / 64);
-        nic::note_kernelf("bf16_wx_kernel<1,1,%d>", EPI);
-        hipLaunchKernelGGL((bf16_wx_kernel<1, 1, EPI>), dim3((unsigned)tiles), dim3(kThreads), 0, s, p);
-    }
+    const nic::Bf16WxTile t = nic::bf16_wx_tile(p.M, p.ncols, nic::cu_count());   // 128 x 128 tiles for big launches, else 64 x 64
+    nic::note_kernelf("bf16_wx_kernel<%d,%d,%d>", t.mt_nt, t.mt_nt, EPI);
+    if (t.mt_nt == 2) hipLaunchKernelGGL((bf16_wx_kernel<2, 2, EPI>), dim3((unsigned)t.grid), dim3(kThreads), 0, s, p);
+    else hipLaunchKernelGGL((bf16_wx_kernel<1, 1, EPI>), dim3((unsigned)t.grid), dim3(kThreads), 0, s, p);
     return 0;
 }
 

@@ -13,7 +13,7 @@
 // Production kernels (16-byte aligned operands — everything the rollout engine allocates):
 //   gemm_wx_dma_kernel     forward + dgrad; 128 x 128 x 32 block tile of 8 waves (2 x 4, wave tile 64 x 32), two workgroups
 //                          co-resident per CU; 64 x 128 (8 waves) and 32 x 128 (4 waves) for small launches / thin or ragged
-//                          outputs (pick_wx_tile; round 4: co-resident workgroups beat one 256 x 256 workgroup per CU)
+//                          outputs (pick_wx_tile in wx_plan.h; round 4: co-resident workgroups beat one 256 x 256 workgroup per CU)
 //   gemm_wgrad_dma_kernel  weight gradient, 128 x 256 output tile per (scenario chunk, period group), 8 waves (2 x 4)
 //   both: tiles go HBM/L2 -> LDS by `buffer_load_dwordx4 ... lds` (no VGPR round trip), double-buffered, one barrier per
 //   k tile; A-style tiles [rows][32] are unpadded with a 16-byte-chunk XOR swizzle applied on the DMA source address
@@ -25,7 +25,8 @@
 //             free because parity is defined to 1e-5, not bitwise, for the policy GEMMs.
 // Fallback kernels (gemm_wx_kernel, gemm_wgrad_kernel): register-staged, per-element guards, for unaligned operands,
 // scenario counts that are not a multiple of 32, and the thin layers of the weight gradient.
-// Dispatch: forward / dgrad in dispatch_wx below; the weight gradient (kernel, slab slots, chunk, flush, launches) in wgrad_plan.h.
+// Dispatch: forward / dgrad (kernel, grid, reported name) in wx_plan.h, launched by dispatch_wx below; the weight gradient (kernel,
+// slab slots, chunk, flush, launches) in wgrad_plan.h.  Both headers are plain C++ that the host tests run without a GPU.
 // Roofline: MFMA-bound.  Measured on MI355X (512 x 512 x 65,536): 102-114 TFLOP/s; MFMA pipe 70 % busy at a 2.26 GHz
 // sustained clock (profiles/r01_gemm_pmc_dma256.txt); the remainder is the per-tile DMA wait + barrier (a no-DMA timing
 // build runs 117 TFLOP/s) and the unoverlapped prologue / epilogue of a 1-workgroup-per-CU kernel.
@@ -33,6 +34,7 @@
 
 #include "nic_common.h"
 #include "wgrad_plan.h"
+#include "wx_plan.h"
 
 namespace {
 
@@ -654,7 +656,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_wx_dma_kernel(WxP
 // KS wavefronts of a workgroup split the contraction (K / KS each) and add their accumulators through LDS once, so even a
 // 17-row logits layer at 1,024 scenarios is 32 tiles x 4 = 128 wavefronts with 8 k groups each instead of one 16-tile chain.
 // Operand traffic is tiles x K x 32 (1 + NT) x 4 B from L2 (weights and the activations of a small batch are L2-resident):
-// only worth it while that stays below ~100 MB - pick_wx_stream.
+// only worth it while that stays below ~100 MB - pick_wx_stream (wx_plan.h).
 // Same k order as the LDS-DMA kernel within a group (lanes 0-31: k = kk, lanes 32-63: k = 8 + kk).
 // ---------------------------------------------------------------------------------------------------------------
 template <int NT, int KS, int EPI>
@@ -1274,165 +1276,99 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ slab, int64_t lds_
     else if (db) db[n] = s;
 }
 
-// fast (buffer-load) path: 16-byte aligned operands, row strides multiples of 4 floats, buffers below 2 GiB
-bool wx_fast_ok(const WxParams& p) {
-    return p.lda % 4 == 0 && p.ldb % 4 == 0 && (reinterpret_cast<uintptr_t>(p.A) & 15) == 0 &&
-           (reinterpret_cast<uintptr_t>(p.Bm) & 15) == 0 && (int64_t)p.M * p.lda < (1ll << 28) &&
-           (int64_t)p.K * p.ldb < (1ll << 28);
-}
-
-#ifdef NIC_TUNING_BUILD
-int wx_lds_pad() {  // NIC_WX_LDS_PAD: unused dynamic LDS per workgroup = fewer co-resident workgroups per CU (occupancy experiments)
-    const char* e = getenv("NIC_WX_LDS_PAD");
-    return e ? atoi(e) : 0;
-}
-#else
-constexpr int wx_lds_pad() { return 0; }
-#endif
-
-template <int WM, int WN, int MT, int NT, int EPI>
-void launch_wx_dma(const WxParams& p, hipStream_t s) {
-    constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
-    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.ncols + BN - 1) / BN;
-    nic::note_kernelf("gemm_wx_dma_kernel<%d,%d,%d,%d,%s>", WM, WN, MT, NT, epi_name(EPI));
-    hipLaunchKernelGGL((gemm_wx_dma_kernel<WM, WN, MT, NT, EPI>), dim3(tiles_m * tiles_n), dim3(64 * WM * WN), wx_lds_pad(), s, p);
-}
-
-template <int WM, int WN, int MT, int NT, int EPI>
-void launch_wx(const WxParams& p, hipStream_t s) {
-    constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
-    const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.ncols + BN - 1) / BN;
-    nic::note_kernelf("gemm_wx_kernel<%d,%d,%d,%d,%s>", WM, WN, MT, NT, epi_name(EPI));
-    hipLaunchKernelGGL((gemm_wx_kernel<WM, WN, MT, NT, EPI>), dim3(tiles_m * tiles_n), dim3(kThreads), 0, s, p);
-}
-
-// A/B variants of the dispatch (1 = 128 x 128 tiles for the big layers, 2 = register-staged wgrad, 3 = wgrad without the XCD
-// tile order) exist only in the tuning build tools/gemm_probe.py makes for itself (-DNIC_TUNING_BUILD, a separate .so
-// outside the package); the product library has no environment switches: every variant below is a correct kernel, but
-// which one runs must not depend on a stray variable.
+// ---- forward / input gradient: launches.  WHICH kernel runs, over which grid, is decided in wx_plan.h ---------------------------
+// The tuning switches below (and the A/B variants of the dispatch: 1 = 128 x 128 tiles for the big layers, 2 = register-staged
+// wgrad, 3 = wgrad without the XCD tile order) exist only in the tuning build tools/gemm_probe.py makes for itself
+// (-DNIC_TUNING_BUILD, a separate .so outside the package); the product library has no environment switches: every variant is a
+// correct kernel, but which one runs must not depend on a stray variable.
 #ifdef NIC_TUNING_BUILD
 extern "C" int nic_tuning_set_stamps(void* buf) {  // buf: device memory, 8 x u64 per workgroup of the next launches (or null)
     unsigned long long* pbuf = static_cast<unsigned long long*>(buf);
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_nic_stamps), &pbuf, sizeof(pbuf));
 }
-int tune_flags() {  // NIC_GEMM_TUNE: timing experiments inside the wx kernel (see WxParams::tune); read at every launch
-    const char* e = getenv("NIC_GEMM_TUNE");
-    return e ? atoi(e) : 0;
+int env_int(const char* name, int unset) {  // read at every launch
+    const char* e = getenv(name);
+    return e ? atoi(e) : unset;
 }
+int wx_lds_pad() { return env_int("NIC_WX_LDS_PAD", 0); }  // unused dynamic LDS per workgroup = fewer co-resident workgroups per CU
+int tune_flags() { return env_int("NIC_GEMM_TUNE", 0); }   // timing experiments inside the wx kernel (see WxParams::tune)
+int forced_wx_tile() { return env_int("NIC_WX_TILE", -1); }      // tiling id for every wx launch (tools/gemm_tile_probe.py)
+int forced_wx_stream() { return env_int("NIC_WX_STREAM", -1); }  // 0 = never, 10 * NT + KS = that instantiation; unset = the picker
 int gemm_variant() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("NIC_GEMM_VARIANT");
-        v = e ? atoi(e) : 0;
-    }
+    static int v = env_int("NIC_GEMM_VARIANT", 0);
     return v;
 }
+nic::WxForce wx_force(const WxParams& p) {   // NIC_WX_TILE in range wins over tune bit 128 (the 256 x 256 tiling)
+    const int tile = forced_wx_tile();
+    return {forced_wx_stream(), tile >= 0 && tile < 4 ? tile : (p.tune & 128 ? 3 : -1)};
+}
+constexpr int kWxKernels = nic::WX_KERNEL_END;
 #else
-constexpr int gemm_variant() { return 0; }
+constexpr int kWxKernels = nic::WX_PRODUCT_END;   // no force, so no tuning-only kernel: tests/test_wx_plan_host.py
+constexpr int wx_lds_pad() { return 0; }
 constexpr int tune_flags() { return 0; }
+constexpr int gemm_variant() { return 0; }
+constexpr nic::WxForce wx_force(const WxParams&) { return {}; }
 #endif
 
-// Tile shape of the LDS-DMA wx kernel.  Round 4 measured seventeen tilings from 1,024 to 65,536 scenarios
-// (tools/gemm_tile_probe.py, profiles/r04_gemm_tile_probe*.json) and what decides is NOT bytes of LDS traffic per flop but how
-// many workgroups a CU holds at once: a lone 256 x 256 workgroup (128 KB of LDS, one per CU) spends ~0.5-1.2 us of every k tile
-// in the copy's round trip + the barrier with nothing else to issue, while two co-resident 128 x 128 workgroups of 8 waves
-// (64 KB each, 65-90 VGPRs) cover each other's stalls: 512 x 512 x 65,536 dgrad 278 -> 262 us (0.786 -> 0.833 of the FP32 MFMA
-// peak), forward 267 = 267; at 8,192 scenarios (cfg3's shard on 8 GPUs) 73 -> 38-40 us, at 1,024 (the reference's shipped
-// batch) 70 -> 14 us.  Round 3's picker counted whole rounds of 256 CUs only, so every launch of fewer than 256 tiles "cost one
-// round" whatever the tile and ran as 16-128 big workgroups.  Three tilings remain:
-//   128 x 128, 8 waves (wave tile 64 x 32), 2 per CU   launches that fill both slots of every CU (>= 512 tiles)
-//    64 x 128, 8 waves (wave tile 32 x 32), 3 per CU   smaller launches with >= 33 output rows
-//    32 x 128, 4 waves (wave tile 32 x 32), 4 per CU   thin outputs (17 logits rows) and ragged heights (393 rows: 13 row
-//                                                      blocks of 32 instead of 4 of 128 - measured 229 us against 252 for
-//                                                      round 3's 448-row tile)
-// chosen by rows computed per row of the matrix (padding to the block height) x the measured relative cost of the tiling.
-// The 256 x 256 tiling only exists in tuning builds (A/B reference of the probes).
-enum WxTile { WX_128x128W8, WX_64x128W8, WX_32x128, WX_256x256, WX_N };
-int pick_wx_tile(int M, int ncols) {
-    auto padded = [&](int bm) { return (double)((M + bm - 1) / bm * bm) / M; };
-    const int64_t tiles128 = (int64_t)((M + 127) / 128) * ((ncols + 127) / 128);
-    double c128 = padded(128), c64 = padded(64) * 1.02, c32 = padded(32) * 1.06;   // (512 x 512 x 65,536: 262 / 265 / 281 us)
-    if (tiles128 < 2 * nic::cu_count()) {   // fewer than two workgroups per CU: smaller tiles put more wavefronts on a CU
-        c128 = 1e30;
-        c64 = padded(64);
-        c32 = padded(32) * 1.02;
-    }
-    if (c128 <= c64 && c128 <= c32) return WX_128x128W8;
-    return c64 <= c32 ? WX_64x128W8 : WX_32x128;
+// one launcher per kernel family; each holds its template arguments to the kernel's line in nic::kWxGeometry (name, grid, block)
+constexpr bool wx_geometry_is(nic::WxKernel id, nic::WxFamily family, int a0, int a1, int a2, int a3, int bm, int bn, int threads) {
+    const nic::WxGeometry& g = nic::kWxGeometry[id];
+    return g.family == family && g.targs[0] == a0 && g.targs[1] == a1 && g.targs[2] == a2 && g.targs[3] == a3 && g.bm == bm &&
+           g.bn == bn && g.threads == threads;
+}
+template <nic::WxKernel ID, int WM, int WN, int MT, int NT, int EPI>
+void launch_wx_dma(const WxParams& p, int grid, hipStream_t s) {
+    static_assert(wx_geometry_is(ID, nic::WX_DMA, WM, WN, MT, NT, WM * MT * 32, WN * NT * 32, 64 * WM * WN), "nic::kWxGeometry");
+    hipLaunchKernelGGL((gemm_wx_dma_kernel<WM, WN, MT, NT, EPI>), dim3(grid), dim3(64 * WM * WN), wx_lds_pad(), s, p);
+}
+template <nic::WxKernel ID, int WM, int WN, int MT, int NT, int EPI>
+void launch_wx(const WxParams& p, int grid, hipStream_t s) {
+    static_assert(wx_geometry_is(ID, nic::WX_STAGED, WM, WN, MT, NT, WM * MT * 32, WN * NT * 32, kThreads), "nic::kWxGeometry");
+    hipLaunchKernelGGL((gemm_wx_kernel<WM, WN, MT, NT, EPI>), dim3(grid), dim3(kThreads), 0, s, p);
+}
+template <nic::WxKernel ID, int NT, int KS, int EPI>
+void launch_wx_stream(const WxParams& p, int grid, hipStream_t s) {
+    static_assert(wx_geometry_is(ID, nic::WX_STREAM, NT, KS, 0, 0, 32, 32 * NT, 64 * KS), "nic::kWxGeometry");
+    hipLaunchKernelGGL((gemm_wx_stream_kernel<NT, KS, EPI>), dim3(grid), dim3(64 * KS), 0, s, p);
 }
 
+// the instantiation behind every nic::WxKernel, in the enum's order
+template <int EPI>
+void (*const kWxLaunch[])(const WxParams&, int grid, hipStream_t) = {
+    launch_wx_stream<nic::WX_STREAM_1x2, 1, 2, EPI>, launch_wx_stream<nic::WX_STREAM_1x4, 1, 4, EPI>,
+    launch_wx_dma<nic::WX_DMA_128x128, 2, 4, 2, 1, EPI>, launch_wx_dma<nic::WX_DMA_64x128, 2, 4, 1, 1, EPI>,
+    launch_wx_dma<nic::WX_DMA_32x128, 1, 4, 1, 1, EPI>,
+    launch_wx<nic::WX_STAGED_128x128, 2, 2, 2, 2, EPI>, launch_wx<nic::WX_STAGED_64x128, 1, 4, 2, 1, EPI>,
+    launch_wx<nic::WX_STAGED_32x256, 1, 4, 1, 2, EPI>,
 #ifdef NIC_TUNING_BUILD
-int forced_wx_tile() {  // NIC_WX_TILE: tiling id for every wx launch (tools/gemm_tile_probe.py); read at every launch
-    const char* e = getenv("NIC_WX_TILE");
-    return e ? atoi(e) : -1;
-}
-#else
-constexpr int forced_wx_tile() { return -1; }
+    launch_wx_stream<nic::WX_STREAM_1x1, 1, 1, EPI>, launch_wx_stream<nic::WX_STREAM_2x1, 2, 1, EPI>,
+    launch_wx_stream<nic::WX_STREAM_2x2, 2, 2, EPI>, launch_wx_stream<nic::WX_STREAM_2x4, 2, 4, EPI>,
+    launch_wx_dma<nic::WX_DMA_256x256, 2, 4, 4, 2, EPI>,
 #endif
+};
 
-// Streamed form (gemm_wx_stream_kernel) for launches of at most 1,024 output tiles of 32 x 32: NT = 1 (every tile its own
-// wavefront), KS = wavefronts that split the contraction, so that the launch has ~2,048 wavefronts where K allows.
-// Returns 0 (LDS-DMA kernels) or KS.  Measured (tools/gemm_tile_probe.py --stream, profiles/r04_gemm_stream_probe.json; us per
-// launch, LDS-DMA -> streamed): 512 x 512 x 1,024 scenarios 21.7 -> 10.5, x 2,048 22.8 -> 15.7, x 4,096 25.0 -> 29.4 (not taken);
-// logits 17 x 512 13.2 -> 7.5 up to 8,192 scenarios, 14.5 -> 9.3 at 16,384; first-layer input gradient 51 x 512 20.6 -> 7.6.
-int pick_wx_stream(int M, int K, int ncols) {
-    const int64_t tiles = (int64_t)((M + 31) / 32) * ((ncols + 31) / 32);
-    const int cus = nic::cu_count();
-    if (tiles > 4 * cus || K < 128) return 0;   // (a short contraction is 2-4 k tiles of the LDS pipeline: nothing to gain, measured)
-    int ks = 1;
-    while (ks < 4 && tiles * ks * 2 <= 8 * cus && K >= 64 * ks * 2) ks *= 2;
-    return ks;
+// what nic_last_kernel() reports for each of them: formatted once, by the header
+template <int EPI>
+struct WxKernelNames {
+    char name[kWxKernels][64];
+    WxKernelNames() { for (int k = 0; k < kWxKernels; ++k) nic::wx_kernel_name(name[k], sizeof(name[k]), static_cast<nic::WxKernel>(k), epi_name(EPI)); }
+};
+template <int EPI>
+const WxKernelNames<EPI>& wx_kernel_names() {
+    static const WxKernelNames<EPI> names;
+    return names;
 }
-
-template <int NT, int KS, int EPI>
-void launch_wx_stream(const WxParams& p, hipStream_t s) {
-    const int tiles = ((p.M + 31) / 32) * ((p.ncols + 32 * NT - 1) / (32 * NT));
-    nic::note_kernelf("gemm_wx_stream_kernel<%d,%d,%s>", NT, KS, epi_name(EPI));
-    hipLaunchKernelGGL((gemm_wx_stream_kernel<NT, KS, EPI>), dim3(tiles), dim3(64 * KS), 0, s, p);
-}
-
-#ifdef NIC_TUNING_BUILD
-int forced_wx_stream() {  // NIC_WX_STREAM: 0 = never, 10 * NT + KS = that instantiation for every wx launch; unset = the picker
-    const char* e = getenv("NIC_WX_STREAM");
-    return e ? atoi(e) : -1;
-}
-#else
-constexpr int forced_wx_stream() { return -1; }
-#endif
 
 template <int EPI>
 void dispatch_wx(const WxParams& p, hipStream_t s) {
-    if (wx_fast_ok(p)) {
-        int stream = 10 + pick_wx_stream(p.M, p.K, p.ncols);
-        if (stream == 10) stream = 0;
-        if (forced_wx_stream() >= 0) stream = forced_wx_stream();
-        switch (stream) {
-            case 11: launch_wx_stream<1, 1, EPI>(p, s); return;
-            case 12: launch_wx_stream<1, 2, EPI>(p, s); return;
-            case 14: launch_wx_stream<1, 4, EPI>(p, s); return;
-#ifdef NIC_TUNING_BUILD
-            case 21: launch_wx_stream<2, 1, EPI>(p, s); return;
-            case 22: launch_wx_stream<2, 2, EPI>(p, s); return;
-            case 24: launch_wx_stream<2, 4, EPI>(p, s); return;
-#endif
-            default: break;
-        }
-        // production path: LDS-DMA kernels
-        int tile = pick_wx_tile(p.M, p.ncols);
-#ifdef NIC_TUNING_BUILD
-        if (p.tune & 128) tile = WX_256x256;
-        if (forced_wx_tile() >= 0 && forced_wx_tile() < WX_N) tile = forced_wx_tile();
-        if (tile == WX_256x256) { launch_wx_dma<2, 4, 4, 2, EPI>(p, s); return; }
-#endif
-        switch (tile) {
-            case WX_128x128W8: launch_wx_dma<2, 4, 2, 1, EPI>(p, s); return;
-            case WX_64x128W8: launch_wx_dma<2, 4, 1, 1, EPI>(p, s); return;
-            default: launch_wx_dma<1, 4, 1, 1, EPI>(p, s); return;
-        }
-    }
-    if (p.M > 64) launch_wx<2, 2, 2, 2, EPI>(p, s);        // unaligned operands: guarded register-staged kernels
-    else if (p.M > 32) launch_wx<1, 4, 2, 1, EPI>(p, s);
-    else launch_wx<1, 4, 1, 2, EPI>(p, s);
+    const bool operands = nic::wx_operands(reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.Bm), p.lda, p.ldb, p.M, p.K);
+    const nic::WxPlan plan = nic::wx_plan(p.M, p.K, p.ncols, operands, nic::cu_count(), wx_force(p));
+    nic::note_kernel(wx_kernel_names<EPI>().name[plan.kernel]);
+    // (asserted here and not next to the array: the array's first use decides where the compiler emits the wx kernels, and they stay
+    // behind the weight-gradient kernels, as before the table)
+    static_assert(sizeof(kWxLaunch<EPI>) / sizeof(kWxLaunch<EPI>[0]) == kWxKernels, "one launcher per nic::WxKernel this build can plan");
+    kWxLaunch<EPI>[plan.kernel](p, plan.grid, s);
 }
 
 // ---- weight gradient: launches.  WHICH kernel runs, over which slots, is decided in wgrad_plan.h ----------------------------------

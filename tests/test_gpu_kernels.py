@@ -19,6 +19,7 @@ from neural_inventory_control_amd.layout import pad_ld, to_soa
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 import record_wgrad_pins  # noqa: E402
+import record_wx_pins  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -595,6 +596,24 @@ def test_wgrad_dispatch_is_pinned_to_the_parent(case):
     print(f"PIN {case[0]}: {got} (recorded: {want})")
     assert got["kernel"] == want["kernel"]
     assert got["used_slots"] == want["used_slots"]
+    if want["sha256"] is not None:
+        assert got["sha256"] == want["sha256"]
+
+
+def _wx_pins():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wx_dispatch_pins.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("case_id,direction", record_wx_pins.PIN_RUNS, ids=record_wx_pins.PIN_IDS)
+def test_wx_dispatch_is_pinned_to_the_parent(case_id, direction):
+    """The forward / input-gradient dispatch does what it did before the launch plan moved into csrc/wx_plan.h: for the smallest
+    shapes that reach each branch on 256 compute units (tools/record_wx_pins.py, recorded there twice on an MI355X at the commit
+    before; the two recordings agreed in every bit) the same kernel and a bit-identical output, NaN padding columns included."""
+    want = _wx_pins()[f"{case_id}-{direction}"]
+    got = record_wx_pins.run_pin_case(case_id, direction)
+    print(f"PIN {case_id}-{direction}: {got} (recorded: {want})")
+    assert got["kernel"] == want["kernel"]
     if want["sha256"] is not None:
         assert got["sha256"] == want["sha256"]
 

@@ -1,5 +1,5 @@
 """Times every tile shape of the LDS-DMA wx kernel (forward / dgrad) over scenario counts from the reference's shipped batch size
-(1,024) to BASELINE cfg3's 65,536, next to what `pick_wx_tile` chooses by itself, and the all-period weight-gradient contraction
+(1,024) to BASELINE cfg3's 65,536, next to what `pick_wx_tile` (csrc/wx_plan.h) chooses by itself, and the all-period weight-gradient contraction
 with the period-group split.  Calibrates `kKtileFloor` / `kFixed` of csrc/linear_mfma.hip::wx_cost.
 
 Forcing a tile needs the tuning build (-DNIC_TUNING_BUILD reads NIC_WX_TILE at every launch); the product library has no such
