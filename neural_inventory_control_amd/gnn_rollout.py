@@ -19,7 +19,8 @@ they would compute there), and every sum over a node's edges still adds them in 
 import torch
 
 from . import _lib, ops
-from .layout import demand_trace_soa, ProblemCache, Table
+from .launch_replay import LaunchReplay, ReplayedEngine
+from .layout import demand_trace_soa, free_hbm, ProblemCache, Table
 from .ops import EnvState, Mlp3Segment
 
 MODULES = ("initial_node", "initial_edge", "node_update", "edge_update", "output")
@@ -200,7 +201,7 @@ class _Mlp:
             self.packed_t.copy_(tr)
 
 
-class GnnRollout:
+class GnnRollout(ReplayedEngine):
     @staticmethod
     def supports(model, problem_params=None):
         if type(model).__name__ != "GNN" or not hasattr(model, "nn_args"):
@@ -235,11 +236,10 @@ class GnnRollout:
         self.fused_bwd = None
         self.keep_inputs = False  # "hist": True = also keep a copy of the gathered MLP inputs (while it fits) instead of reading
         #                         them again from their per-period sources in the backward (same speed, 40 % more history)
-        # replay the (static) launch sequence of a rollout from a HIP graph after one eager run: True / False, or "auto" (what
-        # `Trainer` sets, as on the MLP engine) = decided by MEASUREMENT on the second training run of a shape - if the host needs
-        # longer to enqueue the ~27 launches per period than the GPU needs to run them, later runs are replayed (the reference's
-        # shipped batch of 1,024 scenarios: 19.2 -> 14.6 ms per step; 8,192 scenarios are GPU-bound and stay eager)
-        self.use_graph = False
+        # `use_graph`: replay the ~27 launches per period and their descriptor builds from HIP graphs - True / False / "auto" (what
+        # `Trainer` sets; launch_replay.py, which holds all of the launch-mode state).  The reference's shipped batch of 1,024
+        # scenarios: 19.2 -> 14.6 ms per step; 8,192 scenarios are GPU-bound and stay eager
+        self._replay = LaunchReplay()
         self.fuse_alloc_env = True   # one-warehouse graphs: allocation head + env step (and their adjoints) in one launch each
         # Forward of a period as ONE launch (csrc/gnn_period.hip: the five MLPs on embeddings held in LDS, + allocation and env step
         # on one-warehouse graphs) instead of ~8: "auto" = wherever the graph's embeddings fit in LDS and the backward reads the
@@ -260,16 +260,11 @@ class GnnRollout:
         #               in the sweep, so that this engine matches the reference's golden numbers on such graphs (single process only:
         #               the coupling crosses shard boundaries)
         self.zero_lead_orders = "drop"
-        self._auto_graph = None
-        self.auto_graph_probe = None
         self._probs = ProblemCache()
         self._key = None
 
     def _k(self, tag, fn, *a, **kw):
         return fn(*a, **kw) if self.timer is None else self.timer.call(tag, fn, *a, **kw)
-
-    def _graph_on(self):
-        return self.use_graph is True or (self.use_graph == "auto" and self._auto_graph is True)
 
     # ---- setup --------------------------------------------------------------------------------------------------------------
     def shapes_ok(self, data):
@@ -329,8 +324,7 @@ class GnnRollout:
             # rows of history per period: H1 + H2 of the five MLPs, and their gathered inputs
             h_bytes = 4 * T * ld * 64 * (2 * N + 3 * E)
             x_bytes = 4 * T * ld * (N * (self.Dn + 96) + E * (65 + 96 + 32))
-            free = (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-                    if dev.type == "cuda" else 0)
+            free = free_hbm(dev)
             mode = "fused" if h_bytes > 0.6 * free else "hist"
             self._keep_inputs = h_bytes + x_bytes <= 0.6 * free
         self._mode_now = mode or "hist"
@@ -345,7 +339,7 @@ class GnnRollout:
                                n_live=P.n_live if name in ("edge_update", "output") else None,
                                dense=dense)
                     for name, k, ne in zip(MODULES, ks, ents)}
-        self._graphs, self._eager_runs, self._auto_graph = {}, 0, None   # (a new shape is measured afresh)
+        self._replay.reset(buffers=False)   # (a new shape is measured afresh)
         self._period, self._pdesc, self.edge_scratch = False, {}, None
         self._slab_flat = None
         if train:   # the fifteen weight-gradient slabs as views of one allocation: one fill per step zeroes them all
@@ -453,8 +447,8 @@ class GnnRollout:
                 pairs = prob._zero_lead_pairs = tuple((s_, j_) for s_ in range(lt0.shape[0]) for j_ in range(lt0.shape[1])
                                                       if float(lt0[s_, j_]) == 0.0)
             self._zl_pairs = pairs
-        if (self.zero_lead_orders, self._zl_pairs) != getattr(self, "_graph_rule", None):   # captured launches embody the rule
-            self._graph_rule, self._graphs, self._eager_runs = (self.zero_lead_orders, self._zl_pairs), {}, 0
+        replay = self._replay
+        if replay.set_variant((self.zero_lead_orders, self._zl_pairs)):   # captured launches embody the rule
             self._pdesc, self._bdesc = {}, {}   # (... and so do the cached launch descriptors)
         P.lead[0, :P.n_int].copy_(data["lead_times"][0][P.lead_store, P.lead_wh])
         P.lead[0, P.n_int:P.n_int + P.Wn].copy_(data["warehouse_lead_times"][0, :P.Wn])
@@ -468,33 +462,19 @@ class GnnRollout:
             f[:, mi + 1, :Wn, :B] = data["warehouse_edge_costs"].t()
         for r, k in enumerate(("holding_costs", "underage_costs", "mean", "std")):
             f[:, mi + r, Wn:, :B] = data[k].t()
-        if self._graph_on():  # captured launches point at engine-owned buffers: keep the demand trace in one of them
-            if getattr(self, "_demand_buf", None) is None or self._demand_buf.shape != demand_soa.shape:
-                self._demand_buf, self._graphs, self._eager_runs = torch.empty_like(demand_soa), {}, 0
-            if self._demand_buf.data_ptr() != demand_soa.data_ptr():
-                self._demand_buf.copy_(demand_soa)
-            demand_soa = self.demand = self._demand_buf
-            if getattr(self, "_graph_prob", None) is not None and self._graph_prob.same_layout(prob):
-                self._graph_prob.copy_tables_from(prob)
-                prob = self.prob = self._graph_prob
-            else:
-                self._graph_prob, self._graphs, self._eager_runs = prob, {}, 0
+        # captured launches point at buffers that stay: the demand trace staged in one, the first run's tables refreshed in place
+        demand_soa = self.demand = replay.stage_demand(demand_soa)
+        prob = self.prob = replay.pin_problem(prob)
 
         def forward():
             for t in range(T):
                 self._forward_period(t, prob, demand_soa, shift)
-        probe = None
-        if self.use_graph == "auto" and self._auto_graph is None and train and self._eager_runs >= 1 and self.timer is None:
-            import time
-            probe = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            torch.cuda.synchronize()
-            probe[0].record()
-            probe_t0 = time.perf_counter()
-        self._replay_or_capture(("fwd", T, shift, bool(train)), forward)
+        replay.probe_begin(train, self.timer)
+        replay.call(("fwd", T, shift, bool(train)), forward, self.timer)
         total = self.rewards.sum()
         reported = self.rewards[ignore_periods:].sum() if ignore_periods else total
         if not train:
-            self._eager_runs += 1
+            replay.ran()
             return total, reported
         if grad_scale is None:
             grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
@@ -509,15 +489,9 @@ class GnnRollout:
                 self._backward_period(t, prob, demand_soa, shift, g_next, g_cur)
                 g_next, g_cur = g_cur, g_next
             self._weight_gradients(T, prob)
-        self._replay_or_capture(("bwd", T, shift), backward)
-        if probe is not None:   # host time to enqueue the step against GPU time to run it (one synchronisation, once per shape)
-            host_ms = (time.perf_counter() - probe_t0) * 1e3
-            probe[1].record()
-            probe[1].synchronize()
-            gpu_ms = probe[0].elapsed_time(probe[1])
-            self._auto_graph = host_ms > 0.85 * gpu_ms
-            self.auto_graph_probe = {"host_enqueue_ms": host_ms, "gpu_ms": gpu_ms, "replay": self._auto_graph}
-        self._eager_runs += 1
+        replay.call(("bwd", T, shift), backward, self.timer)
+        replay.probe_end()
+        replay.ran()
         if assign_grads:
             for p, g in self.param_grads():
                 p.grad = g
@@ -527,20 +501,6 @@ class GnnRollout:
         """[(parameter, gradient buffer of the last training run)] - engine-owned buffers, overwritten by the next run."""
         return [(t, g) for m in self.mlp.values() for i, lin in enumerate(m.linears)
                 for t, g in ((lin.weight, m.gw[i]), (lin.bias, m.gb[i]))]
-
-    def _replay_or_capture(self, name, fn):
-        """The launch sequence of a rollout is identical from call to call (same buffers, same shapes): after one eager run
-        it is captured into a HIP graph and replayed, which removes the host cost of ~3,000 launches and descriptor builds."""
-        if not self._graph_on() or self.timer is not None or self._eager_runs < 1:
-            return fn()
-        g = self._graphs.get(name)
-        if g is None:
-            g = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            with torch.cuda.graph(g):
-                fn()
-            self._graphs[name] = g
-        g.replay()
 
     def _weight_gradients(self, T, prob):
         """dW = sum over the slab slots the backward kernels added their per-workgroup weight gradients to."""

@@ -58,6 +58,38 @@ def demand_trace_soa(d, ldb, device=None):
     return out
 
 
+def free_hbm(device):
+    """Bytes of HBM a new buffer can take: what the driver reports + what torch's caching allocator holds but is not using."""
+    if device.type != "cuda":
+        return 0
+    return torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+
+
+def fill_observation_rows(X, f_dyn, S, P, T, B, shift, data, demand_soa, dpad):
+    """data_driven: the observation rows behind the `f_dyn` state rows of every period's input block, in the reference's
+    concatenation order (neural_networks.py:452-470): past demands [S][P] (the window demands[t+shift-P : t+shift], zeros to
+    the left of period 0: environment.py:436-458), underage [S], holding [S], days_from_christmas [D] (column
+    min(t+shift, last): :460-468), lead times [S][W].  A handful of strided copies for ALL periods.
+    X: the blocks as a [T][F][ld] view of any strides (the whole-horizon route keeps them [F][T][ld] and passes the transpose);
+    dpad: [P + periods of the trace][S][ld] scratch whose first P periods are zero.  Returns the row behind the last one filled."""
+    ld, o = X.shape[-1], f_dyn
+    dpad[P:].copy_(demand_soa)      # P zero periods in front: the window of period t is rows [t+shift, t+shift+P)
+    win = dpad.as_strided((T, S, P, ld), (S * ld, ld, S * ld, 1), shift * S * ld)
+    X[:, o:o + S * P].unflatten(1, (S, P)).copy_(win)
+    o += S * P
+    for k in ("underage_costs", "holding_costs"):
+        X[:, o:o + S, :B] = data[k].t()
+        o += S
+    dfc = data["days_from_christmas"]                      # [B][D][periods of the data]
+    D = dfc.shape[1]
+    idx = torch.clamp(torch.arange(T, device=X.device) + shift, max=dfc.shape[2] - 1)
+    X[:, o:o + D, :B] = dfc[:, :, idx].permute(2, 1, 0)
+    o += D
+    lt = data["lead_times"]                                 # [B][S][W]
+    X[:, o:o + lt.shape[1] * lt.shape[2], :B] = lt.reshape(B, -1).t()
+    return o + lt.shape[1] * lt.shape[2]
+
+
 class Table:
     """A per-location table (loc[, supplier], scenario) with explicit element strides; keeps the tensor alive."""
 

@@ -18,12 +18,15 @@ many-warehouse vanilla head's logits layer runs on its LIVE rows only (pairs wit
 The host loop issues ~6 launches per period forward and ~11 backward and never synchronises; the only device->host
 transfers are the two scalars the trainer reports.
 """
+from collections import namedtuple
+
 import torch
 
 from . import _lib, ops
 from . import horizon_rollout as hz
 from . import small_rollout as sr
-from .layout import demand_trace_soa, EnvProblem, ProblemCache, Table, pad_ld
+from .launch_replay import LaunchReplay, ReplayedEngine
+from .layout import demand_trace_soa, fill_observation_rows, free_hbm, EnvProblem, ProblemCache, Table
 from .ops import EnvState
 
 _HEADS = {"vanilla_one_store": "softplus", "vanilla_warehouse": "warehouse", "vanilla_serial": "serial",
@@ -99,7 +102,11 @@ class KernelTimer:
         self.names = {}
 
 
-class FusedRollout:
+# what the launch sequences of one per-period run read (Wv / Wtv: views of the engine's weights and their transposes, unpadded)
+_Ctx = namedtuple("_Ctx", "prob T B ld shift train Wv Wtv biases L demand")
+
+
+class FusedRollout(ReplayedEngine):
     @staticmethod
     def supports(model):
         name = getattr(model, "nn_args", {}).get("name") if hasattr(model, "nn_args") else None
@@ -139,12 +146,9 @@ class FusedRollout:
         self.head = _HEADS[model.nn_args["name"]]
         self._key = None
         self.timer = None  # KernelTimer or None
-        # replay the launch sequence from a HIP graph (see _replay_or_capture): True / False, or "auto" = decided by MEASUREMENT
-        # on the second training run of a shape: if the host needs longer to enqueue the ~13 launches per period than the GPU
-        # needs to run them (small batches on a slow or busy host), the step is launch-bound and later runs are replayed
-        self.use_graph = False
-        self._auto_graph = None   # "auto": None = not measured yet, else the decision; `auto_graph_probe` = what was measured
-        self.auto_graph_probe = None
+        # `use_graph`: replay the ~13 launches per period from HIP graphs - True / False / "auto" (launch_replay.py, which holds
+        # all of the launch-mode state; graph keys "fwd" / "bwd")
+        self._replay = LaunchReplay()
         self.use_small = True   # whole-horizon kernels for the small one-store-chain policies (small_rollout.py)
         self.small_lane_scenarios = 0  # ... 16 or 32 scenarios per wavefront (0: 16 while 32 would leave SIMDs without a wavefront)
         self.small_wgrad_in_kernel = True  # ... with the weight gradients contracted inside the backward kernel (False: dZ history + one GEMM per layer)
@@ -188,7 +192,13 @@ class FusedRollout:
         self.eval_history = None  # evaluation keeps per-period states/orders/logits: None = while small, True / False = forced
         self.small = None       # SmallRolloutPlan when the current shapes take that route
         self._prob_cache = ProblemCache()
-        self._prob = None
+        self.inputs_versioned = False   # (opt-in, see _copy_if_changed)
+        self._copied = {}
+        self._shift_hint = 0
+        self._wide_shapes = self._wide_bwd = False
+        self._tail_slots = 0
+        self._ub_cache = (None, None)
+        self._dpad = self._thin = self._hz_checked = self.sr_scratch = self._g_reward_key = None
 
     def _k(self, tag, fn, *args, **kw):
         if self.timer is None:
@@ -203,7 +213,7 @@ class FusedRollout:
 
     def _use_wide(self):
         """the whole-horizon forward kernel of the wide policy (csrc/wide_rollout.hip) runs for the current shapes and options"""
-        return getattr(self, "_wide_shapes", False) and not self._round
+        return self._wide_shapes and not self._round
 
     def _use_tail(self):
         """the fused per-period tail launches (csrc/period_tail.hip) run for the current shapes and options"""
@@ -211,11 +221,8 @@ class FusedRollout:
 
     def _use_tail_bwd(self):
         """the backward tail launch: forced on -> always; "auto" -> from tail_bwd_min_scenarios up, or when launched eagerly"""
-        return (self._use_tail() and getattr(self, "_tail_slots", 0) > 0
+        return (self._use_tail() and self._tail_slots > 0
                 and (self.fuse_tail is True or self.prob.B >= self.tail_bwd_min_scenarios or not self._graph_on()))
-
-    def _graph_on(self):
-        return self.use_graph is True or (self.use_graph == "auto" and self._auto_graph is True)
 
     # ---- buffers ------------------------------------------------------------------------------------------------
     def _linears(self):
@@ -250,13 +257,12 @@ class FusedRollout:
     def _setup(self, prob, T, train, extra_rows=0):
         key = (prob.B, T, bool(train), prob.S, prob.Wn, prob.E, prob.Ws, prob.Ww, prob.We, self.batch_wgrad, self.use_thin,
                self.eval_history, self.small_wgrad_in_kernel, extra_rows, self.small_lane_scenarios, self.use_horizon,
-               self.horizon_max_scenarios, getattr(self, "_shift_hint", 0), self.fuse_tail, self.tail_max_scenarios,
+               self.horizon_max_scenarios, self._shift_hint, self.fuse_tail, self.tail_max_scenarios,
                self.tail_bwd_min_scenarios, self.fuse_head_env, self.use_wide, check_gemm_precision(self.gemm_precision))
         if self._key == key:
             return
         dev, ld = self.device, prob.ldb
-        self._prob = None
-        self._auto_graph = None   # (a new shape is measured afresh)
+        self._replay.reset()   # (a new shape is measured afresh)
         for name in ("states", "orders", "logits", "hidden", "dZhist", "dZlast_hist", "dH", "slabs", "sr_states", "sr_hidden",
                      "sr_logits", "sr_dzh", "sr_dzo", "sr_slab", "sr_grad", "hz_X", "hz_z1", "hz_hist", "hz_dz"):
             setattr(self, name, None)  # release the previous shapes' buffers before sizing the new ones
@@ -325,7 +331,7 @@ class FusedRollout:
         hz_limit = self.horizon_max_scenarios * (4 if prob.S * prob.nsup <= 8 else 1)
         if (self.use_horizon and extra_rows > 0 and prob.B <= hz_limit and all(m.bias is not None for m in lins)
                 and hz.HorizonPlan.supports(prob, self.head, dims)
-                and hz.offsets_ok(prob, T, T + getattr(self, "_shift_hint", 0), hz.MAX_HIDDEN)):
+                and hz.offsets_ok(prob, T, T + self._shift_hint, hz.MAX_HIDDEN)):
             # ---- whole-horizon route for data_driven: one forward kernel, one backward kernel, four GEMMs over (period x scenario)
             # columns (the observation rows' share of the first layer; one weight gradient per layer).  Histories [row][T][ld].
             plan = self.horizon = hz.HorizonPlan(prob, dims)
@@ -348,7 +354,6 @@ class FusedRollout:
                 self.slabs = [z(self.splits[i], dims[i + 1], (dims[i] + 1 + 3) // 4 * 4) for i in range(L)]
                 self.gw = [torch.zeros_like(m.weight) for m in lins]
                 self.gb = [torch.zeros_like(m.bias) for m in lins]
-            self.demand_buf, self._graphs, self._eager_runs = None, {}, 0
             self._key = key
             return
         # Many-warehouse vanilla head: the logits of (store, warehouse) pairs without an edge are never read upstream
@@ -379,9 +384,7 @@ class FusedRollout:
         f_tot = self.F_store + self.F_wh + self.F_ech + extra_rows
         # evaluation keeps the state / order / logit history only while it is small (tests and short horizons read it);
         # a long-horizon evaluation (test periods: 5000) rolls through two state blocks and one order / logit block
-        free_now = (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-                    if dev.type == "cuda" else 0)
-        auto = 4 * (T + 1) * ld * (f_tot + n_ord + dims[-1]) <= 0.1 * free_now
+        auto = 4 * (T + 1) * ld * (f_tot + n_ord + dims[-1]) <= 0.1 * free_hbm(dev)
         self._hist = bool(train) or extra_rows > 0 or (auto if self.eval_history is None else bool(self.eval_history))
         # (+ one row of ONES behind every period's block: with the bias as row K of the transposed first-layer weights the bias is one
         # more term of the first layer's contraction - the streamed first-layer forward then issues no bias loads, see _launch_forward)
@@ -436,11 +439,8 @@ class FusedRollout:
             # BASELINE cfg3 — HBM is sized for it): their weight gradients are contracted once per training step over
             # (period x scenario) instead of once per period (see _launch_backward)
             hist_bytes = 4 * T * ld * sum(gd[1:])
-            # free HBM = what the driver reports + what torch's caching allocator holds but is not using
-            free_bytes = (torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
-                          if dev.type == "cuda" else 0)
             # not enough HBM left for the gradient history -> accumulate weight gradients period by period
-            batch = self.batch_wgrad and hist_bytes <= 0.6 * free_bytes
+            batch = self.batch_wgrad and hist_bytes <= 0.6 * free_hbm(dev)
             self.dZhist = [zpad(T, dims[i + 1], ld) for i in range(L - 1)] if batch else None
             # ... and the logits gradient too, unless the logits layer takes the fused thin-layer backward (per period)
             thin_last = L > 1 and self.use_thin and ops.linear_bwd_thin_ok(gd[L], gd[L - 1])
@@ -467,9 +467,6 @@ class FusedRollout:
             if self.live_rows is not None:   # the compact logits layer reduces into these; scattered into gw / gb afterwards
                 self.gw_c = z(gd[-1], gd[-2])
                 self.gb_c = z(gd[-1]) if lins[-1].bias is not None else None
-        self.demand_buf = None
-        self._graphs = {}      # "fwd"/"bwd" -> torch.cuda.CUDAGraph (HIP graph) of the launch sequence
-        self._eager_runs = 0
         if self.head == "warehouse":
             self.adj = self.model.adjacency(prob.S, prob.Wn, dev)
         if self.head == "data_driven" and prob.Wn:
@@ -501,7 +498,7 @@ class FusedRollout:
         if not torch.is_tensor(ub):
             return float(ub)
         key = (ub.data_ptr(), ub._version)
-        if getattr(self, "_ub_cache", (None, None))[0] != key:
+        if self._ub_cache[0] != key:
             self._ub_cache = (key, float(ub.reshape(-1)[0]))
         return self._ub_cache[1]
 
@@ -533,24 +530,13 @@ class FusedRollout:
             extra = prob.S * P_ + 2 * prob.S + data["days_from_christmas"].shape[1] + prob.S * data["lead_times"].shape[2]
         self._shift_hint = observation_params["demand"]["period_shift"] if observation_params else 0
         self._setup(prob, T, train, extra)
-        if self._graph_on():
-            # a captured graph holds raw pointers: keep the first call's table tensors and refresh their CONTENTS
-            if self._prob is not None and self._prob.same_layout(prob):
-                self._prob.copy_tables_from(prob)
-                prob = self._prob
-            else:
-                self._prob, self._graphs, self._eager_runs = prob, {}, 0
-        self.prob = prob
-        shift = observation_params["demand"]["period_shift"] if observation_params else 0
+        replay = self._replay
+        # a captured graph holds raw pointers: it reads the first call's table tensors and a staged demand trace, refreshed in place
+        self.prob = prob = replay.pin_problem(prob)
+        shift = self._shift_hint
         if demand_soa is None:
             demand_soa = demand_trace_soa(data["demands"], ld, dev)
-        if self._graph_on():
-            if self.demand_buf is None or self.demand_buf.shape != demand_soa.shape:
-                self.demand_buf, self._graphs, self._eager_runs = torch.empty_like(demand_soa), {}, 0
-            if self.demand_buf.data_ptr() != demand_soa.data_ptr():
-                self.demand_buf.copy_(demand_soa)
-            demand_soa = self.demand_buf
-        self.demand = demand_soa
+        self.demand = demand_soa = replay.stage_demand(demand_soa)
         if demand_soa.shape[0] < T + shift:
             raise ValueError("Current period is greater than the number of periods in the data")
 
@@ -601,26 +587,20 @@ class FusedRollout:
             s0.ech[:, :, :B].copy_(data["initial_echelon_inventories"].permute(1, 2, 0))
 
         if self.head == "data_driven":
-            self._fill_observation_rows(data, prob, T, B, ld, shift, observation_params, demand_soa)
+            self._fill_observation_rows(self.states[:T], data, prob, T, shift, observation_params, demand_soa)
         self._ub_now = self._ub() if self.head not in ("softplus", "data_driven") else 0.0
-        self._ctx = (prob, T, B, ld, shift, train, Wv, Wtv, biases, L, demand_soa)
-        probe = None
-        if self.use_graph == "auto" and self._auto_graph is None and train and self._eager_runs >= 1 and self.timer is None:
-            import time
-            probe = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            torch.cuda.synchronize()
-            probe[0].record()
-            probe_t0 = time.perf_counter()
-        self._replay_or_capture("fwd", self._launch_forward)
+        self._ctx = _Ctx(prob, T, B, ld, shift, train, Wv, Wtv, biases, L, demand_soa)
+        if replay.on():   # options baked into a captured launch sequence
+            replay.set_variant((self._round, shift, self.fuse_head_env, self.fuse_tail, self.use_wide, self._use_tail_bwd()))
+        replay.probe_begin(train, self.timer)
+        replay.call("fwd", self._launch_forward, self.timer)
         total = self.rewards.sum()
         reported = self.rewards[ignore_periods:].sum() if ignore_periods else total
         if not train:
-            self._eager_runs += 1
+            replay.ran()
             return total, reported
 
-        if grad_scale is None:
-            grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
-        self._set_g_reward(B, grad_scale)
+        self._set_g_reward(B, T, grad_scale)
         tail = self._use_tail_bwd()
         for i, sl in enumerate(self.slabs):
             if not (tail and i == len(self.slabs) - 1):
@@ -631,18 +611,12 @@ class FusedRollout:
             self.g_state[0].zero_()
         # layers whose backward is ONE fused pass over their input (nic_linear_bwd_thin): thin output, not the first
         thin = [i > 0 and self.use_thin and ops.linear_bwd_thin_ok(self.gd[i + 1], self.gd[i]) for i in range(len(lins))]
-        if thin != getattr(self, "_thin", None):
+        if thin != self._thin:
             self._thin = thin
-            self._graphs.pop("bwd", None)  # a captured launch sequence no longer applies
-        self._replay_or_capture("bwd", self._launch_backward)
-        if probe is not None:   # host time to enqueue the step against GPU time to run it (one synchronisation, once per shape)
-            host_ms = (time.perf_counter() - probe_t0) * 1e3
-            probe[1].record()
-            probe[1].synchronize()
-            gpu_ms = probe[0].elapsed_time(probe[1])
-            self._auto_graph = host_ms > 0.85 * gpu_ms
-            self.auto_graph_probe = {"host_enqueue_ms": host_ms, "gpu_ms": gpu_ms, "replay": self._auto_graph}
-        self._eager_runs += 1
+            replay.graphs.pop("bwd", None)  # a captured launch sequence no longer applies
+        replay.call("bwd", self._launch_backward, self.timer)
+        replay.probe_end()
+        replay.ran()
         if assign_grads:
             self._assign_grads(accumulate_grads)
         return total, reported
@@ -659,56 +633,15 @@ class FusedRollout:
                      + S * data["lead_times"].shape[2])
         return rows
 
-    def _fill_observation_rows_by_row(self, X, data, prob, T, B, ld, shift, observation_params, demand_soa):
-        """The same rows as `_fill_observation_rows` in the whole-horizon route's [row][T][ld] order (X: [F][T][ld])."""
-        S, P_ = prob.S, observation_params["demand"]["past_periods"]
-        o = self.F_dyn
-        n_t = demand_soa.shape[0]
-        if getattr(self, "_dpad", None) is None or self._dpad.shape != (P_ + n_t, S, ld):
-            self._dpad = torch.zeros(P_ + n_t, S, ld, device=self.device)
-        self._dpad[P_:].copy_(demand_soa)
-        # row (s, p) of period t = demand of period t + shift - P + p = padded row t + shift + p
-        win = self._dpad.as_strided((S, P_, T, ld), (ld, S * ld, S * ld, 1), shift * S * ld)
-        X[o:o + S * P_].view(S, P_, T, ld).copy_(win)
-        o += S * P_
-        for k in ("underage_costs", "holding_costs"):
-            X[o:o + S, :, :B] = data[k].t().unsqueeze(1)
-            o += S
-        dfc = data["days_from_christmas"]                      # [B][D][periods of the data]
-        D = dfc.shape[1]
-        idx = torch.clamp(torch.arange(T, device=self.device) + shift, max=dfc.shape[2] - 1)
-        X[o:o + D, :, :B] = dfc[:, :, idx].permute(1, 2, 0)
-        o += D
-        lt = data["lead_times"]                                 # [B][S][W]
-        X[o:o + lt.shape[1] * lt.shape[2], :, :B] = lt.reshape(B, -1).t().unsqueeze(1)
-        assert o + lt.shape[1] * lt.shape[2] == self.F
-
-    def _fill_observation_rows(self, data, prob, T, B, ld, shift, observation_params, demand_soa):
-        """data_driven: the observation rows behind the state rows of every period's input block, in the reference's
-        concatenation order (neural_networks.py:452-470): past demands [S][P] (the window demands[t+shift-P : t+shift], zeros to
-        the left of period 0: environment.py:436-458), underage [S], holding [S], days_from_christmas [D] (column
-        min(t+shift, last): :460-468), lead times [S][W].  A handful of strided copies for ALL periods, outside the period loop."""
-        S, P_ = prob.S, observation_params["demand"]["past_periods"]
-        X = self.states                       # [T+1][F][ld]
-        o = self.F_dyn
-        n_t = demand_soa.shape[0]
-        if getattr(self, "_dpad", None) is None or self._dpad.shape != (P_ + n_t, S, ld):
-            self._dpad = torch.zeros(P_ + n_t, S, ld, device=self.device)
-        self._dpad[P_:].copy_(demand_soa)      # P zero periods in front: the window of period t is rows [t+shift, t+shift+P)
-        win = self._dpad.as_strided((T, S, P_, ld), (S * ld, ld, S * ld, 1), shift * S * ld)
-        X[:T, o:o + S * P_].view(T, S, P_, ld).copy_(win)
-        o += S * P_
-        for k in ("underage_costs", "holding_costs"):
-            X[:T, o:o + S, :B] = data[k].t()
-            o += S
-        dfc = data["days_from_christmas"]                      # [B][D][periods of the data]
-        D = dfc.shape[1]
-        idx = torch.clamp(torch.arange(T, device=self.device) + shift, max=dfc.shape[2] - 1)
-        X[:T, o:o + D, :B] = dfc[:, :, idx].permute(2, 1, 0)
-        o += D
-        lt = data["lead_times"]                                 # [B][S][W]
-        X[:T, o:o + lt.shape[1] * lt.shape[2], :B] = lt.reshape(B, -1).t()
-        assert o + lt.shape[1] * lt.shape[2] == self.F
+    def _fill_observation_rows(self, X, data, prob, T, shift, observation_params, demand_soa):
+        """data_driven: the observation rows of every period's input block (X: the blocks as a [T][F][ld] view), outside the period
+        loop (layout.fill_observation_rows)."""
+        P_ = observation_params["demand"]["past_periods"]
+        shape = (P_ + demand_soa.shape[0], prob.S, prob.ldb)
+        if self._dpad is None or self._dpad.shape != shape:
+            self._dpad = torch.zeros(shape, device=self.device)
+        end = fill_observation_rows(X, self.F_dyn, prob.S, P_, T, prob.B, shift, data, demand_soa, self._dpad)
+        assert end == self.F
 
     def param_grads(self):
         """[(parameter, gradient buffer of the last training run)] - engine-owned buffers, overwritten by the next run."""
@@ -723,7 +656,7 @@ class FusedRollout:
         """(total, reported) = sums of the per-period costs [T][ldb] (all periods / periods >= ignore_periods, trainer.py:207-210)
         by `nic_small_rollout_reduce`: two launches, fixed order, no semaphore pass."""
         need = sr.small_rollout_reduce_scratch(0, 0, self.rewards.numel())
-        if getattr(self, "sr_scratch", None) is None or self.sr_scratch.numel() < need:
+        if self.sr_scratch is None or self.sr_scratch.numel() < need:
             self.sr_scratch, self.sr_totals = torch.empty(need, device=self.device), torch.zeros(2, device=self.device)
         sr.small_rollout_reduce(None, 0, None, self.rewards, ignore_periods, self.sr_totals, self.sr_scratch)
         tt = self.sr_totals.clone()   # (the caller's tensors must not change under a later step)
@@ -734,19 +667,30 @@ class FusedRollout:
         when `src` is the very tensor (same object, same in-place version) that was copied into the same destination last time.
         torch's version counter does not see every write - raw-pointer kernels (the HIP sampler), `.data` assignments, `set_()` -
         so by default every presented batch is copied: one small launch."""
-        if not getattr(self, "inputs_versioned", False):
+        if not self.inputs_versioned:
             dst.copy_(src.permute(1, 2, 0))
             return
-        cache = self.__dict__.setdefault("_copied", {})
         key = (dst.data_ptr(), tuple(dst.shape), src._version)
-        hit = cache.get(slot)
+        hit = self._copied.get(slot)
         if hit is not None and hit[0] is src and hit[1] == key:
             return
         dst.copy_(src.permute(1, 2, 0))
-        cache[slot] = (src, key)
+        self._copied[slot] = (src, key)
 
-    def _set_g_reward(self, B, grad_scale):
-        self._g_reward_key = sr.set_g_reward(self.g_reward, B, grad_scale, getattr(self, "_g_reward_key", None))
+    def _set_g_reward(self, B, T, grad_scale):
+        """g_reward <- d(loss)/d(reward[b, t]); default 1 / (B * T * S) = trainer.py:169"""
+        if grad_scale is None:
+            grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
+        self._g_reward_key = sr.set_g_reward(self.g_reward, B, grad_scale, self._g_reward_key)
+
+    def _wgrad_over_columns(self, tag, inputs, dzs, n_cols):
+        """Weight gradients of a whole-horizon route: per layer ONE contraction of the pre-activation gradients `dzs[i]` with the
+        layer's inputs over (period, scenario) = `n_cols` columns, both [rows][T][ld]; padding columns of `dzs` are zero."""
+        for i, (x, dz) in enumerate(zip(inputs, dzs)):
+            n, k = self.dims[i + 1], self.dims[i]
+            self.slabs[i].zero_()
+            self._k(f"{tag}_{n}x{k}", ops.linear_wgrad, dz.flatten(1), x.flatten(1), self.slabs[i], n_cols)
+            ops.wgrad_reduce(self.slabs[i], self.gw[i], self.gb[i], k, 1.0)
 
     def _assign_grads(self, accumulate):
         sr.assign_grads(self.param_grads(), accumulate)
@@ -780,9 +724,7 @@ class FusedRollout:
             total, reported = self._cost_totals(ignore_periods)
         if not train:
             return total, reported
-        if grad_scale is None:
-            grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
-        self._set_g_reward(B, grad_scale)
+        self._set_g_reward(B, T, grad_scale)
         if self.small_wgrad_in_kernel:
             self._k("small_rollout_bwd", sr.small_rollout_bwd_wgrad, desc, *hist, Table(self.g_reward, 0, 1), self.sr_slab)
             # the step's two sums - partial gradients over the wavefronts, costs over (period, scenario) - in two small launches
@@ -790,7 +732,7 @@ class FusedRollout:
             # (the row sums end in a semaphore pass with its own memset).
             n_rows = sr.slab_rows_written(B, width)
             need = sr.small_rollout_reduce_scratch(n_rows, self.sr_grad.numel(), self.rewards.numel())
-            if getattr(self, "sr_scratch", None) is None or self.sr_scratch.numel() < need:
+            if self.sr_scratch is None or self.sr_scratch.numel() < need:
                 self.sr_scratch, self.sr_totals = torch.empty(need, device=self.device), torch.zeros(2, device=self.device)
             self._k("small_rollout_reduce", sr.small_rollout_reduce, self.sr_slab, n_rows, self.sr_grad, self.rewards, ignore_periods,
                     self.sr_totals, self.sr_scratch)
@@ -800,15 +742,10 @@ class FusedRollout:
                 self._assign_grads(accumulate_grads)
             return total, reported
         self._k("small_rollout_bwd", sr.small_rollout_bwd, desc, *hist, Table(self.g_reward, 0, 1), self.sr_dzh, self.sr_dzo)
-        # weight gradients: contraction over (period, scenario) = T*ld columns; padding columns of dZ are zero
-        n_cols, nh = T * ld, plan.n_hidden
+        nh = plan.n_hidden
         inputs = [self.sr_states[:self.dims[0]]] + [self.sr_hidden[sr.H * l:sr.H * (l + 1)] for l in range(nh)]
         dzs = [self.sr_dzh[sr.H * l:sr.H * (l + 1)] for l in range(nh)] + [self.sr_dzo]
-        for i, m in enumerate(lins):
-            self.slabs[i].zero_()
-            dy, x = dzs[i].reshape(dzs[i].shape[0], n_cols), inputs[i].reshape(inputs[i].shape[0], n_cols)
-            self._k(f"wgrad_{self.dims[i + 1]}x{self.dims[i]}", ops.linear_wgrad, dy, x, self.slabs[i], n_cols)
-            ops.wgrad_reduce(self.slabs[i], self.gw[i], self.gb[i], self.dims[i], 1.0)
+        self._wgrad_over_columns("wgrad", inputs, dzs, T * ld)
         if assign_grads:
             self._assign_grads(accumulate_grads)
         return total, reported
@@ -824,13 +761,13 @@ class FusedRollout:
         if prob.Wn:
             self.hz_state0[a:].view(prob.Wn, prob.Ww, ld)[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
         X = self.hz_X
-        self._fill_observation_rows_by_row(X, data, prob, T, B, ld, shift, observation_params, demand_soa)
+        self._fill_observation_rows(X.transpose(0, 1), data, prob, T, shift, observation_params, demand_soa)
         # the observation rows' share of the first layer for every period at once (+ bias): independent of the rollout
         self.hz_W1obs[:, :Fo].copy_(lins[0].weight.detach()[:, FD:])
         self._k(f"fwdT_{dims[1]}x{Fo}", ops.linear_fwd, self.hz_W1obs[:, :Fo], lins[0].bias.detach(), X[FD:].view(Fo, n_cols),
                 self.hz_z1.view(dims[1], n_cols), n_cols, _lib.NIC_ACT_NONE)
         desc = plan.desc(prob, T, shift, lins, self.edge_mask, demand_soa, n_cols, round_orders=self._round)
-        if getattr(self, "_hz_checked", None) != self._key:   # once per shape: the library's own limits
+        if self._hz_checked != self._key:   # once per shape: the library's own limits
             if not hz.horizon_ok(desc):
                 raise _HorizonRefused()
             self._hz_checked = self._key
@@ -840,67 +777,38 @@ class FusedRollout:
         reported = self.rewards[ignore_periods:].sum() if ignore_periods else total
         if not train:
             return total, reported
-        if grad_scale is None:
-            grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
-        self._set_g_reward(B, grad_scale)
+        self._set_g_reward(B, T, grad_scale)
         self._k("horizon_bwd", hz.horizon_bwd, desc, *hist, Table(self.g_reward, 0, 1), *self.hz_dz)
-        # weight gradients: contractions over (period, scenario) = T * ld columns; padding columns of the dz histories are zero
-        inputs = [X, self.hz_hist[0], self.hz_hist[1]]
-        for i in range(len(lins)):
-            self.slabs[i].zero_()
-            dy, x = self.hz_dz[i].view(dims[i + 1], n_cols), inputs[i].view(dims[i], n_cols)
-            self._k(f"wgradT_{dims[i + 1]}x{dims[i]}", ops.linear_wgrad, dy, x, self.slabs[i], n_cols)
-            ops.wgrad_reduce(self.slabs[i], self.gw[i], self.gb[i], dims[i], 1.0)
+        self._wgrad_over_columns("wgradT", [X, self.hz_hist[0], self.hz_hist[1]], self.hz_dz, n_cols)
         if assign_grads:
             self._assign_grads(accumulate_grads)
         return total, reported
 
-    # ---- launch sequences (eager, or captured once into a HIP graph and replayed) ---------------------------------
-    def _replay_or_capture(self, name, fn):
-        """`use_graph`: the launch sequence of a rollout is identical from call to call (same buffers, same shapes), so it
-        is captured once into a HIP graph and replayed — this removes the per-launch host cost that bounds the small
-        (32-wide) policies, whose kernels run for a few microseconds each.  The first call always runs eagerly (module
-        loading is not capturable); timers force eager mode."""
-        if not self._graph_on() or self.timer is not None or self._eager_runs < 1:
-            return fn()
-        variant = (self._round, self._ctx[4], self.fuse_head_env, self.fuse_tail, self.use_wide, self._use_tail_bwd())  # options baked into the captured launch sequence
-        if getattr(self, "_graph_variant", variant) != variant:
-            self._graphs = {}
-        self._graph_variant = variant
-        g = self._graphs.get(name)
-        if g is None:
-            g = torch.cuda.CUDAGraph()
-            torch.cuda.synchronize()
-            with torch.cuda.graph(g):
-                fn()
-            self._graphs[name] = g
-        g.replay()
-
     # ---- the GEMMs of one layer: FP32 (linear_mfma.hip), or bf16 (linear_bf16.hip) for the layers in bf16_layers -------------
     # (layer i > 0 of the per-period routes; its input is the previous layer's ELU output)
     def _linear_fwd(self, i, x, y):
-        B, biases, n, k = self._ctx[2], self._ctx[8], self.gd[i + 1], self.gd[i]
+        c, n, k = self._ctx, self.gd[i + 1], self.gd[i]
         if i in self.Wb:
-            self._k(f"fwd_bf16_{n}x{k}", ops.linear_bf16_fwd, self.Wb[i][:, :k], biases[i], x, y, B, _lib.NIC_ACT_ELU)
+            self._k(f"fwd_bf16_{n}x{k}", ops.linear_bf16_fwd, self.Wb[i][:, :k], c.biases[i], x, y, c.B, _lib.NIC_ACT_ELU)
         else:
-            self._k(f"fwd_{n}x{k}", ops.linear_fwd, self._ctx[6][i], biases[i], x, y, B, _lib.NIC_ACT_ELU)
+            self._k(f"fwd_{n}x{k}", ops.linear_fwd, c.Wv[i], c.biases[i], x, y, c.B, _lib.NIC_ACT_ELU)
 
     def _linear_dgrad(self, i, d, x_in, dx):
-        B, n, k = self._ctx[2], self.gd[i + 1], self.gd[i]
+        B, n, k = self._ctx.B, self.gd[i + 1], self.gd[i]
         if i in self.Wtb:
             self._k(f"dgrad_bf16_{n}x{k}", ops.linear_bf16_dgrad, self.Wtb[i][:k, :n], d, x_in, dx, B, _lib.NIC_ACT_ELU, False)
         else:
-            self._k(f"dgrad_{n}x{k}", ops.linear_dgrad, self._ctx[7][i], d, x_in, dx, B, _lib.NIC_ACT_ELU, False)
+            self._k(f"dgrad_{n}x{k}", ops.linear_dgrad, self._ctx.Wtv[i], d, x_in, dx, B, _lib.NIC_ACT_ELU, False)
 
     def _linear_wgrad(self, i, d, x_in):
-        B, n, k = self._ctx[2], self.gd[i + 1], self.gd[i]
+        B, n, k = self._ctx.B, self.gd[i + 1], self.gd[i]
         if i in self.Wb:
             self._k(f"wgrad_bf16_{n}x{k}", ops.linear_bf16_wgrad, d, x_in, self.slabs[i], B)
         else:
             self._k(f"wgrad_{n}x{k}", ops.linear_wgrad, d, x_in, self.slabs[i], B)
 
     def _linear_wgrad_periods(self, i, dz_hist, x_hist):
-        B, n, k = self._ctx[2], self.gd[i + 1], self.gd[i]
+        B, n, k = self._ctx.B, self.gd[i + 1], self.gd[i]
         if i in self.Wb:
             self._k(f"wgradT_bf16_{n}x{k}", ops.linear_bf16_wgrad_periods, dz_hist, x_hist, self.slabs[i], B)
         else:
@@ -972,14 +880,15 @@ class FusedRollout:
                     out=self._views(self.states[nxt], prob), reward=self.rewards[t])
 
     def _tail_desc(self, t, state_block, orders_block):
-        prob, T, B, ld, shift, train, Wv, Wtv, biases, L, demand_soa = self._ctx
+        c = self._ctx
+        prob, ld, shift, Wv, biases, L, demand_soa = c.prob, c.ld, c.shift, c.Wv, c.biases, c.L, c.demand
         return ops.period_tail_desc(prob, state_block, Table(demand_soa[t + shift], ld, 1), orders_block, self.adj, self._ub_now,
                                     bool(self.model.transshipment), Wv[L - 1], biases[L - 1], self.Wt[0][:self.F + 1, :self.gd[1]])
 
     def _launch_forward_wide(self):
         """Forward sweep of the wide policy in ONE launch (csrc/wide_rollout.hip); the histories it leaves are the per-period
         route's (states, orders, logits, hidden activations, rewards), so the backward sweep is unchanged."""
-        prob, T, B, ld, shift, train, Wv, Wtv, biases, L, demand_soa = self._ctx
+        train, L = self._ctx.train, self._ctx.L
         lins = self._linears()
         for l in range(1, L - 1):
             ops.wide_pack_hidden(lins[l].weight, self.Wpk[l - 1])
@@ -989,7 +898,8 @@ class FusedRollout:
         self._k("wide_fwd", ops.wide_rollout_fwd, self._wide_desc(train))
 
     def _wide_desc(self, with_hidden):
-        prob, T, B, ld, shift, train, Wv, Wtv, biases, L, demand_soa = self._ctx
+        c = self._ctx
+        prob, T, shift, biases, L, demand_soa = c.prob, c.T, c.shift, c.biases, c.L, c.demand
         return ops.wide_rollout_desc(prob, T, self.adj, self._ub_now, bool(self.model.transshipment), demand_soa, shift, self.states,
                                      self.orders, self.logits, self.rewards, self.hidden if with_hidden else None,
                                      self.Wt[0][:self.F + 1, :self.gd[1]], self.Wpk, [biases[l] for l in range(1, L - 1)], self.Wq,
@@ -999,7 +909,7 @@ class FusedRollout:
         """Backward sweep of the wide policy: ONE launch walks the periods in reverse over the histories the forward kernel left and
         writes every layer's pre-activation gradient history; the weight gradients are then one (period x scenario) contraction
         per layer, as on the per-period route."""
-        prob, T, B, ld, shift, train, Wv, Wtv, biases, L, demand_soa = self._ctx
+        T, B, L = self._ctx.T, self._ctx.B, self._ctx.L
         lins = self._linears()
         for l in range(1, L - 1):
             ops.wide_pack_hidden(lins[l].weight.detach().t(), self.WpkT[l - 1])
@@ -1022,7 +932,8 @@ class FusedRollout:
     def _launch_forward_tail(self):
         """Forward sweep with the fused tail: [first layer of period 0], then per period the hidden-layer GEMMs and ONE tail launch
         (logits + head + env step + first layer of period t+1) - L - 1 launches per period instead of L + 1."""
-        prob, T, B, ld, shift, train, Wv, Wtv, biases, L, demand_soa = self._ctx
+        c = self._ctx
+        T, B, train, Wv, biases, L = c.T, c.B, c.train, c.Wv, c.biases, c.L
         hist = self._hist
         if self._thin_in and self._thin_in_aug:   # first layer of period 0 (later periods': the tail launch of the period before)
             self._k(f"fwd_{self.gd[1]}x{self.gd[0]}", ops.linear_fwd_thin_in, self.Wt[0][:self.F + 1, :self.gd[1]], None,
@@ -1045,7 +956,7 @@ class FusedRollout:
     def _launch_backward_tail(self):
         """Backward sweep with the fused tail: per period ONE tail launch (first layer's input gradient of period t+1 + env / head
         adjoints + logits layer backward with its weight gradient) and the hidden layers' input gradients."""
-        prob, T, B, ld, shift, train, Wv, Wtv, biases, L, demand_soa = self._ctx
+        T, L = self._ctx.T, self._ctx.L
         g_next, g_cur = self.g_state
         hist = self.dZhist
         g_rew = Table(self.g_reward, 0, 1)
@@ -1075,8 +986,9 @@ class FusedRollout:
             ops.wgrad_reduce(self.slabs[i], self.gw[i], self.gb[i], self.gd[i], 1.0)
 
     def _launch_backward(self):
-        prob, T, B, ld, shift, train, Wv, Wtv, biases, L, demand_soa = self._ctx
-        if self._use_wide() and getattr(self, "_wide_bwd", False):
+        c = self._ctx
+        prob, T, B, ld, shift, Wv, Wtv, L, demand_soa = c.prob, c.T, c.B, c.ld, c.shift, c.Wv, c.Wtv, c.L, c.demand
+        if self._use_wide() and self._wide_bwd:
             return self._launch_backward_wide()
         if self._use_tail_bwd():
             return self._launch_backward_tail()
