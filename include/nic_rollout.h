@@ -422,6 +422,31 @@ int nic_small_rollout_ensemble_reduce(const NicSmallEnsemble* e, const float* sl
                                       float* grad, const float* rewards, int64_t n_reward_elems, int64_t ignore_elems, float* totals,
                                       float* scratch, void* stream);
 
+/* ---- Adam for K models whose parameters are rows of one buffer: two launches per step for all of them -------------------------
+ * Replaces main_run.py:110 (`torch.optim.Adam(model.parameters(), lr=...)`) stepped by trainer.py:177 (`optimizer.step()`), once per
+ * model (K optimizers, or K parameter groups: torch launches per group).  Row m of params / grads / exp_avg / exp_avg_sq starts
+ * m * its stride floats from its base (every stride >= P; columns at or past P are neither read nor written) - the layout is
+ * general, nothing here knows about layers.  The arithmetic is csrc/ensemble_adam_body.h's.
+ * hyper [K][5] doubles {lr, beta1, beta2, eps, weight_decay}, state [K] (below), coef [K][8] floats, all on the device.
+ * `prepare` (one thread per model, all in double): step += 1, c1 *= beta1, c2 *= beta2, then coef = {lr / (1 - c1),
+ * 1 / sqrt(1 - c2), beta1, 1 - beta1, beta2, 1 - beta2, eps, weight_decay}, each rounded to float once.  No pow: the running
+ * products are IEEE on host and device alike.
+ * `update` (float32, one element per thread, after `prepare` on the same stream - it reads coef only, never the counter):
+ *     g' = weight_decay != 0 ? g + weight_decay * p : g
+ *     m  = beta1 * m + (1 - beta1) * g'
+ *     v  = beta2 * v + (1 - beta2) * (g' * g')
+ *     p -= step_size * (m / (sqrt(v) * inv_bc2_sqrt + eps))
+ * Refused (non-zero, message in nic_last_error, nothing launched): n_models outside 1..65535, P < 1, a null pointer, a stride
+ * shorter than P. */
+typedef struct NicEnsembleAdamState {
+    int32_t step, reserved;                /* steps taken */
+    double c1, c2;                         /* beta1^step, beta2^step as running products (1.0 at step 0) */
+} NicEnsembleAdamState;
+int nic_ensemble_adam_prepare(int32_t n_models, const double* hyper, NicEnsembleAdamState* state, float* coef, void* stream);
+int nic_ensemble_adam_update(int32_t n_models, int32_t P, float* params, int64_t params_stride, const float* grads, int64_t grads_stride,
+                             float* exp_avg, int64_t exp_avg_stride, float* exp_avg_sq, int64_t exp_avg_sq_stride, const float* coef,
+                             void* stream);
+
 /* ---- whole-horizon rollout of the closed-form policies ---------------------------------------------------------
  * base_stock (neural_networks.py:216-229), capped_base_stock (:296-311) and echelon_stock (:231-294) for T periods of
  * Trainer.simulate_batch (trainer.py:190-213) in ONE launch, forward AND gradient: one lane per store chain, pipelines in

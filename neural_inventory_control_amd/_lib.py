@@ -84,6 +84,11 @@ class NicSmallEnsembleSlices(C.Structure):
                                          "slab_row_stride", "slab", "grad", "scratch")]
 
 
+class NicEnsembleAdamState(C.Structure):
+    """one model's Adam state on the device: steps taken, beta1^step and beta2^step as running products (include/nic_rollout.h)"""
+    _fields_ = [("step", C.c_int32), ("reserved", C.c_int32), ("c1", C.c_double), ("c2", C.c_double)]
+
+
 class NicHorizonDesc(C.Structure):
     _fields_ = ([("io", NicEnvStepIO)] + [(n, C.c_int32) for n in ("T", "t0", "H1", "H2", "n_out", "round_orders")]
                 + [("W1", C.c_void_p), ("ldw1", C.c_int64), ("W2", C.c_void_p), ("ldw2", C.c_int64), ("W3", C.c_void_p),
@@ -211,6 +216,8 @@ PROTOTYPES = {
     "nic_small_rollout_ensemble_bwd_wgrad": (C.c_int, [C.POINTER(NicSmallRolloutDesc), C.POINTER(NicSmallEnsemble), _vp, _vp, _vp, NicTable2,
                                                        _vp, _i64, _vp]),
     "nic_small_rollout_ensemble_reduce": (C.c_int, [C.POINTER(NicSmallEnsemble), _vp, _i32, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "nic_ensemble_adam_prepare": (C.c_int, [_i32, _vp, _vp, _vp, _vp]),
+    "nic_ensemble_adam_update": (C.c_int, [_i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "nic_horizon_rollout_ok": (C.c_int, [C.POINTER(NicHorizonDesc)]),
     "nic_horizon_rollout_fwd": (C.c_int, [C.POINTER(NicHorizonDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nic_horizon_rollout_bwd": (C.c_int, [C.POINTER(NicHorizonDesc), _vp, _vp, _vp, _vp, _vp, NicTable2, _vp, _vp, _vp, _vp]),

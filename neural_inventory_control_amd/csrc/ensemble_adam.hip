@@ -1,0 +1,58 @@
+// nic_ensemble_adam_prepare / nic_ensemble_adam_update: one Adam step for K models whose parameters, gradients and moments are
+// rows of [K][stride >= P] buffers - two launches for all of them instead of K optimizers' launches (main_run.py:110's
+// `torch.optim.Adam`, stepped by trainer.py:177's `optimizer.step()`).  The arithmetic is csrc/ensemble_adam_body.h's, which the host
+// harness runs too: `prepare` is one thread per model in double, `update` one element per thread in float with plain coalesced
+// loads and stores (K x P is a few tens of thousands of floats and the weights' row stride P is odd: launch latency bounds it).
+// Built with -ffp-contract=off; float division and square root are the correctly rounded ones (hipcc's default).  Nothing here
+// knows about layers.
+#include "nic_common.h"
+#include "ensemble_adam_body.h"
+
+namespace {
+constexpr int kT = nic::kEaThreads;
+
+__global__ __launch_bounds__(kT) void ensemble_adam_prepare_kernel(int n_models, const double* __restrict__ hyper, nic::EaState* __restrict__ state,
+                                                                   float* __restrict__ coef) {
+    const int m = blockIdx.x * kT + threadIdx.x;
+    if (m < n_models) nic::ea_prepare(hyper + (int64_t)m * nic::EA_HYPER_COUNT, state + m, coef + (int64_t)m * nic::EA_COEF_COUNT);
+}
+
+// grid (ceil(P / 256), K): columns at or past P of a row are neither read nor written
+__global__ __launch_bounds__(kT) void ensemble_adam_update_kernel(int P, float* __restrict__ params, int64_t params_stride,
+                                                                  const float* __restrict__ grads, int64_t grads_stride,
+                                                                  float* __restrict__ exp_avg, int64_t exp_avg_stride,
+                                                                  float* __restrict__ exp_avg_sq, int64_t exp_avg_sq_stride,
+                                                                  const float* __restrict__ coef) {
+    const int col = blockIdx.x * kT + threadIdx.x;
+    if (col >= P) return;
+    const int64_t m = blockIdx.y;
+    nic::ea_update(params + m * params_stride + col, grads[m * grads_stride + col], exp_avg + m * exp_avg_stride + col,
+                   exp_avg_sq + m * exp_avg_sq_stride + col, coef + m * nic::EA_COEF_COUNT);
+}
+}  // namespace
+
+extern "C" {
+
+int nic_ensemble_adam_prepare(int32_t n_models, const double* hyper, NicEnsembleAdamState* state, float* coef, void* stream) {
+    const int why = nic::ea_check_prepare(n_models, hyper, state, coef);
+    NIC_REQUIRE(why == 0, "nic_ensemble_adam_prepare: %s (%d models)", nic::ea_reason(why), n_models);
+    nic::note_kernelf("ensemble_adam_prepare<models=%d>", n_models);
+    hipLaunchKernelGGL(ensemble_adam_prepare_kernel, dim3(nic::ceil_div(n_models, kT)), dim3(kT), 0, nic::as_stream(stream), n_models, hyper,
+                       state, coef);
+    return nic::check_launch("nic_ensemble_adam_prepare");
+}
+
+int nic_ensemble_adam_update(int32_t n_models, int32_t P, float* params, int64_t params_stride, const float* grads, int64_t grads_stride,
+                             float* exp_avg, int64_t exp_avg_stride, float* exp_avg_sq, int64_t exp_avg_sq_stride, const float* coef,
+                             void* stream) {
+    const int why = nic::ea_check_update(n_models, P, params, params_stride, grads, grads_stride, exp_avg, exp_avg_stride, exp_avg_sq,
+                                         exp_avg_sq_stride, coef);
+    NIC_REQUIRE(why == 0, "nic_ensemble_adam_update: %s (%d models, P = %d, strides %lld %lld %lld %lld)", nic::ea_reason(why), n_models, P,
+                (long long)params_stride, (long long)grads_stride, (long long)exp_avg_stride, (long long)exp_avg_sq_stride);
+    nic::note_kernelf("ensemble_adam_update<%d,models=%d>", P, n_models);
+    hipLaunchKernelGGL(ensemble_adam_update_kernel, dim3(nic::ceil_div(P, kT), n_models), dim3(kT), 0, nic::as_stream(stream), P, params,
+                       params_stride, grads, grads_stride, exp_avg, exp_avg_stride, exp_avg_sq, exp_avg_sq_stride, coef);
+    return nic::check_launch("nic_ensemble_adam_update");
+}
+
+}  // extern "C"

@@ -7,13 +7,20 @@ with (1,024 - 8,192 scenarios) most SIMDs have no wavefront: seeds, learning rat
 in them instead of paying K steps.  Every model runs the instruction stream of the single-model kernels on its own slice of the
 buffers, so its costs and gradients are the bits `FusedRollout(model).run` gives for it (trainer.py:181-216 once per model).
 
-The launches are eager.  Graph replay, `Trainer` integration, a `torch.library` operator and multi-GPU sharding are not part of
-this engine; the engine owns no optimizer (K optimizers, or one with K parameter groups, step the models independently).
+`run` alone leaves the optimizer to the caller (K optimizers, or one with K parameter groups, step the models independently) and
+packs all K models' weights again every call.  The whole training step is `train_step`: after `bind_parameters()` every model's
+`weight` / `bias` are views of its row of `weights [K][P]` (the packed layout IS `nn.Linear`'s: per layer the weight, row-major,
+then the bias), so nothing is packed, and an `EnsembleAdam` (ensemble_adam.py) updates all K rows with two launches - six
+launches a step (forward, backward, two of the reduction, prepare, update) and no per-model Python.  `use_graph` replays them from
+one captured sequence per batch shape (launch_replay.py); `fit` is the epoch loop over `train_step` with the best weights per
+model kept on the device.  YAML / `main_run` wiring, a `torch.library` operator and multi-GPU sharding are not part of this engine.
 """
 import torch
 
 from . import _lib
 from . import small_rollout as sr
+from .ensemble_adam import EnsembleAdam
+from .launch_replay import LaunchReplay, ReplayedEngine
 from .layout import demand_trace_soa, Table
 from .rollout import _HEADS, FusedRollout
 
@@ -70,7 +77,24 @@ def grad_views(grad, F, n_hidden, n_out):
             for m in range(grad.shape[0])]
 
 
-class SmallPolicyEnsemble:
+class _ShapeState:
+    """What ONE batch shape (the key of `_setup`) owns: the buffers sized for it and the launch-replay state whose captures hold
+    their addresses, its staged demand trace and its pinned problem.  Weights, gradients and optimizer state depend on (K, P)
+    only and are the engine's."""
+    FIELDS = ("plan", "state0", "rewards", "final", "totals", "slices", "scratch", "strides", "ens", "states", "hidden", "logits", "slab",
+              "g_reward", "g_reward_key")
+
+    def __init__(self, use_graph):
+        for name in self.FIELDS:
+            setattr(self, name, None)
+        self.replay = LaunchReplay()
+        self.replay.use_graph = use_graph
+
+
+_MAX_KEPT_SHAPES = 4   # other batch shapes kept while their launches are replayed (an epoch has up to four: full / short x train / dev)
+
+
+class SmallPolicyEnsemble(ReplayedEngine):
     def __init__(self, models, problem_params, device):
         self.models = check_models(models)
         _lib.require_device()
@@ -82,57 +106,144 @@ class SmallPolicyEnsemble:
         self._engines = [FusedRollout(m, problem_params, device) for m in self.models]
         self.small_lane_scenarios = 0   # 16 or 32 scenarios per wavefront (0: small_rollout.lane_width's rule)
         self.last_kernels = {}          # launch class -> kernel name the library recorded in the last run
-        self.plan = None
-        self.states = None
         self._key = None
+        self._shape = _ShapeState(False)   # the current batch shape's buffers and LaunchReplay (read as `ens.rewards`, `ens.plan`, ...)
+        self._shapes = {}               # key -> _ShapeState of the other shapes whose launches are replayed
+        self.weights = self.grad = self._grad_views = None   # [K][P], [K][P rounded up to 4]: once per engine
+        self.param_shapes = None        # shapes of one model's parameters in `parameters()` order (EnsembleAdam's `param_shapes`)
+        self._bind_requested = self._bound = False
+        self._dims_bound = None         # layer sizes, once the parameters are bound
+        self.best_dev = self.best_weights = None   # `fit`: [K] lowest dev loss so far, [K][P] the parameters that gave it
+
+    def __getattr__(self, name):   # (only reached for names the engine itself does not have)
+        if name in _ShapeState.FIELDS:
+            return getattr(self._shape, name)
+        raise AttributeError(name)
 
     @property
     def n_models(self):
         return len(self.models)
 
-    # ---- buffers: once per (B, T, K) ---------------------------------------------------------------------------------------------
-    def _setup(self, prob, T, train):
-        K, dev, ld = self.n_models, self.device, prob.ldb
-        F = prob.S * prob.Ws + (0 if self.head == "softplus" else prob.Wn * prob.Ww + prob.E * prob.We)
+    # ---- launch mode: `use_graph` True / False / "auto" (launch_replay.py) is the engine's, the rest is per batch shape -----------------
+    _replay = property(lambda self: self._shape.replay)
+
+    @property
+    def use_graph(self):
+        return self._shape.replay.use_graph
+
+    @use_graph.setter
+    def use_graph(self, value):
+        self._shape.replay.use_graph = value
+        if value is False:
+            self._shapes = {}   # (nothing is replayed any more: the other shapes' buffers and captures go)
+        for st in self._shapes.values():
+            st.replay.use_graph = value
+
+    # ---- buffers: weights and gradients once per engine, the rest once per (B, T, K) ---------------------------------------------------
+    def _model_buffers(self, dims):
+        n_hidden, n_out = len(dims) - 2, dims[-1]
+        P = sr.packed_weight_count(dims[0], n_hidden, n_out)
+        if self.weights is None:
+            self.weights = torch.zeros(self.n_models, P, device=self.device)
+            self.param_shapes = [shape for _, n, k, _ in sr.layer_slices(dims[0], n_hidden, n_out) for shape in ((n, k), (n,))]
+        assert self.weights.shape[1] == P   # (the models' layer sizes are fixed once they are materialised)
+
+    def _bind(self, lins, dims):
+        """weight.data / bias.data of every layer <- views of the model's row of `weights`, which gets the current values once"""
+        pack_ensemble_weights(lins, self.weights)
+        for m, ls in enumerate(lins):
+            row = self.weights[m]
+            for lin, (o, n, k, bo) in zip(ls, sr.layer_slices(dims[0], len(dims) - 2, dims[-1])):
+                lin.weight.data = row[o:o + n * k].view(n, k)
+                lin.bias.data = row[bo:bo + n]
+        self._bound, self._dims_bound = True, dims
+
+    def bind_parameters(self):
+        """Opt-in: from now on the models' parameters LIVE in `weights [K][P]` (views of their rows), `run` and `train_step` pack
+        nothing, and whatever writes a parameter in place - `load_state_dict`, an optimizer - writes the packed row.  Binds now if
+        the input width is known (a materialised first layer), else on the first batch."""
+        self._bind_requested = True
+        known = [ls[0].in_features for ls in (m.master_linears() for m in self.models)
+                 if not isinstance(ls[0].weight, torch.nn.parameter.UninitializedParameter)]
+        if known and not self._bound:
+            lins = self._materialized(known[0])
+            dims = self._dims(lins)
+            self._model_buffers(dims)
+            self._bind(lins, dims)
+
+    def _materialized(self, F):
         for eng in self._engines:
             eng.materialize(F)
-        lins = [eng._linears() for eng in self._engines]
+        return [eng._linears() for eng in self._engines]
+
+    @staticmethod
+    def _dims(lins):
         dims = [[ls[0].in_features] + [m.out_features for m in ls] for ls in lins]
         for i, d in enumerate(dims):
             if d != dims[0]:
                 raise ValueError(f"model {i}: layer sizes {d} differ from model 0's {dims[0]}")
-        if dims[0][0] != F or not sr.SmallRolloutPlan.supports(prob, self.head, dims[0]):
-            raise ValueError(f"SmallPolicyEnsemble: the whole-horizon kernels do not take this setting / policy (layer sizes {dims[0]}, "
+        return dims[0]
+
+    def _switch_shape(self, key):
+        """Batch shape `key` becomes the current one.  The outgoing shape is kept while its launches are replayed (its captures
+        hold its buffers' addresses; an epoch alternates between a few shapes), else its buffers are released before the new
+        shape is sized."""
+        old = self._shape
+        if self._key is not None and old.replay.on():
+            self._shapes[self._key] = old
+        self._shape = self._shapes.pop(key, None) or _ShapeState(old.replay.use_graph)
+        while len(self._shapes) > _MAX_KEPT_SHAPES:
+            self._shapes.pop(next(iter(self._shapes)))
+        self._key = key
+
+    def _setup(self, prob, T, train):
+        """Sizes what this batch needs; returns the models' layers (None once the parameters are bound: nothing is packed, and the
+        per-model checks were made when they were bound)."""
+        K, dev, ld = self.n_models, self.device, prob.ldb
+        F = prob.S * prob.Ws + (0 if self.head == "softplus" else prob.Wn * prob.Ww + prob.E * prob.We)
+        if self._bound:
+            lins, dims = None, self._dims_bound
+        else:
+            lins = self._materialized(F)
+            dims = self._dims(lins)
+        if dims[0] != F or not sr.SmallRolloutPlan.supports(prob, self.head, dims):
+            raise ValueError(f"SmallPolicyEnsemble: the whole-horizon kernels do not take this setting / policy (layer sizes {dims}, "
                              f"{F} state rows)")
-        key = (prob.B, T, K, tuple(dims[0]), prob.Ws, prob.Wn, prob.Ww, prob.E, prob.We)
+        if not self._bound:
+            self._model_buffers(dims)
+            if self._bind_requested:
+                self._bind(lins, dims)
+                lins = None
+        key = (prob.B, T, K, tuple(dims), prob.Ws, prob.Wn, prob.Ww, prob.E, prob.We)
         if self._key != key:
-            for name in ("states", "hidden", "logits", "slab", "grad", "scratch"):
-                setattr(self, name, None)   # release the previous shapes' buffers before sizing the new ones
-            self.plan = plan = sr.SmallRolloutPlan(prob, self.head, dims[0])
+            self._switch_shape(key)
+        sh = self._shape
+        if sh.plan is None:
+            sh.plan = plan = sr.SmallRolloutPlan(prob, self.head, dims)
             z = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
-            self.weights = z(K, sr.packed_weight_count(F, plan.n_hidden, plan.n_out))
-            self.state0 = z(F, ld)
-            self.rewards, self.final = z(K, T, ld), z(K, F, ld)
-            self.totals = z(K, 2)
+            sh.state0 = z(F, ld)
+            sh.rewards, sh.final = z(K, T, ld), z(K, F, ld)
+            sh.totals = z(K, 2)
             # slice sizes: csrc/small_ensemble_plan.h through the library.  Histories and slab are sized for 16 scenarios per
             # wavefront (as FusedRollout sizes them: the 32-wide form uses the first F / n_out rows and half the slab rows)
-            probe = plan.desc(T, 0, self.weights, self.state0, self.state0, 0.0, prob=prob, lane_scenarios=16)
-            self.slices = s = sr.ensemble_slices(probe)
+            probe = plan.desc(T, 0, self.weights, sh.state0, sh.state0, 0.0, prob=prob, lane_scenarios=16)
+            sh.slices = s = sr.ensemble_slices(probe)
             assert s["weights"] == self.weights.shape[1] and s["rewards"] == T * ld and s["final_state"] == F * ld
-            self.scratch = torch.empty(K, s["scratch"], device=dev)   # (a training step's need; the cost sums alone use less)
-            self.strides = dict(weights=s["weights"], rewards=s["rewards"], final_state=s["final_state"], scratch=s["scratch"])
-            self.ens = sr.ensemble_strides(K, **self.strides)
-            self._key = key
-        if train and self.states is None:
+            sh.scratch = torch.empty(K, s["scratch"], device=dev)   # (a training step's need; the cost sums alone use less)
+            sh.strides = dict(weights=s["weights"], rewards=s["rewards"], final_state=s["final_state"], scratch=s["scratch"])
+            sh.ens = sr.ensemble_strides(K, **sh.strides)
+        if train and sh.states is None:
             # the training buffers come with the first training run of a shape and stay: evaluation runs in between use the rest
-            s, plan = self.slices, self.plan
+            s = sh.slices
             z = lambda *s_: torch.zeros(*s_, device=dev)  # noqa: E731
-            self.states, self.hidden, self.logits = z(K, s["states"]), z(K, s["hidden"]), z(K, s["logits"])
-            self.slab, self.grad = z(K, s["slab_rows"], s["slab_row_stride"]), z(K, s["grad"])
-            self.g_reward, self._g_reward_key = z(ld), None
-            self.strides.update(states=s["states"], hidden=s["hidden"], logits=s["logits"], slab=s["slab"], grad=s["grad"])
-            self._grad_views = grad_views(self.grad, F, plan.n_hidden, plan.n_out)
-            self.ens = sr.ensemble_strides(K, **self.strides)
+            sh.states, sh.hidden, sh.logits = z(K, s["states"]), z(K, s["hidden"]), z(K, s["logits"])
+            sh.slab = z(K, s["slab_rows"], s["slab_row_stride"])
+            sh.g_reward, sh.g_reward_key = z(ld), None
+            if self.grad is None:   # (with the engine's first training run, and kept: it depends on (K, P) only)
+                self.grad = z(K, s["grad"])
+                self._grad_views = grad_views(self.grad, F, sh.plan.n_hidden, sh.plan.n_out)
+            sh.strides.update(states=s["states"], hidden=s["hidden"], logits=s["logits"], slab=s["slab"], grad=s["grad"])
+            sh.ens = sr.ensemble_strides(K, **sh.strides)
         return lins
 
     def param_grads(self):
@@ -155,6 +266,23 @@ class SmallPolicyEnsemble:
         `FusedRollout.run`.  Returns (total [K], reported [K]) device tensors; `rewards` [K][T][ldb] holds the per-period costs."""
         if discrete_allocation and train:
             raise ValueError("discrete_allocation is an evaluation-time option of the fused rollout")
+        tt = self._step(data, periods, ignore_periods, train, observation_params, demand_soa, grad_scale, discrete_allocation, None)
+        if train:
+            sr.assign_grads(self.param_grads(), accumulate_grads)
+        return tt[:, 0], tt[:, 1]
+
+    def train_step(self, data, periods, ignore_periods=0, optimizer=None, observation_params=None, demand_soa=None, grad_scale=None):
+        """One whole training step of all K models: forward, backward, the reduction's two launches and `optimizer`'s two (an
+        `EnsembleAdam` over this engine's (K, P)) - no packing, no `param.grad`, no per-model Python.  Needs `bind_parameters()`.
+        Returns (total [K], reported [K]) of the step BEFORE the update, as `run` does."""
+        if not self._bind_requested:
+            raise ValueError("SmallPolicyEnsemble.train_step needs bound parameters: call bind_parameters() first")
+        if not isinstance(optimizer, EnsembleAdam):
+            raise ValueError("SmallPolicyEnsemble.train_step needs an EnsembleAdam as `optimizer`")
+        tt = self._step(data, periods, ignore_periods, True, observation_params, demand_soa, grad_scale, False, optimizer)
+        return tt[:, 0], tt[:, 1]
+
+    def _step(self, data, periods, ignore_periods, train, observation_params, demand_soa, grad_scale, discrete_allocation, optimizer):
         lead, dev, K = self._engines[0], self.device, self.n_models
         prob = lead._problem_for(data)
         T, B, ld = periods, prob.B, prob.ldb
@@ -164,37 +292,96 @@ class SmallPolicyEnsemble:
         if demand_soa.shape[0] < T + shift:
             raise ValueError("Current period is greater than the number of periods in the data")
         lins = self._setup(prob, T, train)
-        pack_ensemble_weights(lins, self.weights)   # (every run: the optimizers moved the parameters)
+        if optimizer is not None and (optimizer.n_models, optimizer.P) != tuple(self.weights.shape):
+            raise ValueError(f"SmallPolicyEnsemble.train_step: the optimizer is for {optimizer.n_models} models of {optimizer.P} parameters, "
+                             f"the engine has {K} of {self.weights.shape[1]}")
+        sh = self._shape
+        replay = sh.replay
+        # a captured sequence holds raw pointers: it reads the pinned problem's tables and the staged demand trace, refreshed in place
+        prob = replay.pin_problem(prob)
+        demand_soa = replay.stage_demand(demand_soa)
+        if not self._bound:
+            pack_ensemble_weights(lins, self.weights)   # (every run: the optimizers moved the parameters)
         a, b = prob.S * prob.Ws, prob.S * prob.Ws + prob.Wn * prob.Ww
-        self.state0[:a].view(prob.S, prob.Ws, -1)[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
+        sh.state0[:a].view(prob.S, prob.Ws, -1)[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
         if self.head != "softplus":
             if prob.Wn:
-                self.state0[a:b].view(prob.Wn, prob.Ww, -1)[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
+                sh.state0[a:b].view(prob.Wn, prob.Ww, -1)[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
             if prob.E:
-                self.state0[b:b + prob.E * prob.We].view(prob.E, prob.We, -1)[:, :, :B].copy_(
+                sh.state0[b:b + prob.E * prob.We].view(prob.E, prob.We, -1)[:, :, :B].copy_(
                     data["initial_echelon_inventories"].permute(1, 2, 0))
         ub = lead._ub() if self.head != "softplus" else 0.0
         width = sr.lane_width(self.small_lane_scenarios, train, B)
-        desc = self.plan.desc(T, shift, self.weights, demand_soa, self.state0, ub, round_orders=discrete_allocation, prob=prob,
-                              lane_scenarios=width)
-        hist = (self.states, self.hidden, self.logits) if train else (None, None, None)
-        sr.small_rollout_ensemble_fwd(desc, self.ens, self.rewards, self.final, *hist)
-        self._note("fwd")
+        desc = sh.plan.desc(T, shift, self.weights, demand_soa, sh.state0, ub, round_orders=discrete_allocation, prob=prob,
+                            lane_scenarios=width)
+        hist = (sh.states, sh.hidden, sh.logits) if train else (None, None, None)
         n_el = T * ld
         if train:
             if grad_scale is None:
                 grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
-            self._g_reward_key = sr.set_g_reward(self.g_reward, B, grad_scale, self._g_reward_key)
-            row = self.slab.shape[2]
-            sr.small_rollout_ensemble_bwd_wgrad(desc, self.ens, *hist, Table(self.g_reward, 0, 1), self.slab, row)
-            self._note("bwd")
-            sr.small_rollout_ensemble_reduce(self.ens, self.slab, sr.slab_rows_written(B, width), row, self.grad.shape[1], self.grad,
-                                             self.rewards, n_el, ignore_periods * ld, self.totals, self.scratch)
-        else:   # the same reduction, costs only: an evaluation pass returns the very bits a training pass does
-            sr.small_rollout_ensemble_reduce(self.ens, None, 0, 0, 0, None, self.rewards, n_el, ignore_periods * ld, self.totals,
-                                             self.scratch)
-        self._note("reduce")
-        tt = self.totals.clone()   # (the caller's tensors must not change under a later step)
-        if train:
-            sr.assign_grads(self.param_grads(), accumulate_grads)
-        return tt[:, 0], tt[:, 1]
+            sh.g_reward_key = sr.set_g_reward(sh.g_reward, B, grad_scale, sh.g_reward_key)
+
+        def launches():
+            sr.small_rollout_ensemble_fwd(desc, sh.ens, sh.rewards, sh.final, *hist)
+            self._note("fwd")
+            if train:
+                row = sh.slab.shape[2]
+                sr.small_rollout_ensemble_bwd_wgrad(desc, sh.ens, *hist, Table(sh.g_reward, 0, 1), sh.slab, row)
+                self._note("bwd")
+                sr.small_rollout_ensemble_reduce(sh.ens, sh.slab, sr.slab_rows_written(B, width), row, self.grad.shape[1], self.grad,
+                                                 sh.rewards, n_el, ignore_periods * ld, sh.totals, sh.scratch)
+            else:   # the same reduction, costs only: an evaluation pass returns the very bits a training pass does
+                sr.small_rollout_ensemble_reduce(sh.ens, None, 0, 0, 0, None, sh.rewards, n_el, ignore_periods * ld, sh.totals,
+                                                 sh.scratch)
+            self._note("reduce")
+            if optimizer is not None:
+                optimizer.step(self.weights, self.grad)
+
+        # what a captured sequence bakes in besides this shape's buffers.  Engine-wide things are the `variant` (a change drops this
+        # shape's captures now, another shape's when it is current again); the optimizer's buffers, which only a training step's
+        # sequence holds, are part of the capture's key, so evaluations in between (`fit`) change nothing
+        if replay.on():
+            replay.set_variant((K, self.small_lane_scenarios, self.weights.data_ptr(), ub))
+        opt_key = optimizer and tuple(t.data_ptr() for t in (optimizer.hyper, optimizer.state, optimizer.coef, optimizer.exp_avg,
+                                                               optimizer.exp_avg_sq))
+        replay.probe_begin(train)
+        replay.call((train, opt_key, ignore_periods, shift, bool(discrete_allocation), width), launches)
+        replay.probe_end()
+        replay.ran()
+        return sh.totals.clone()   # (outside the capture: the caller's tensors must not change under a later step)
+
+    # ---- epochs ------------------------------------------------------------------------------------------------------------------
+    def fit(self, train_batches, dev_batches, epochs, periods, dev_periods, ignore_periods, optimizer, observation_params=None):
+        """`epochs` times: `train_step` over `train_batches`, then `run(train=False)` over `dev_batches`.  Returns the train and dev
+        histories [epochs][K]: the reported cost per (scenario, reported period, store) as `Trainer.do_one_epoch` averages it.
+        The best dev loss per model and the parameters that gave it are tracked on the device (`best_dev [K]`, `best_weights
+        [K][P]`, updated with a mask): no host synchronisation inside an epoch.  `load_best()` puts them back."""
+        K, dev = self.n_models, self.device
+        hist = [torch.zeros(epochs, K, device=dev), torch.zeros(epochs, K, device=dev)]
+        n_stores = self.problem_params["n_stores"]
+        for epoch in range(epochs):
+            for which, batches, T in ((0, train_batches, periods), (1, dev_batches, dev_periods)):
+                samples = 0
+                for data in batches:
+                    if which == 0:
+                        _, reported = self.train_step(data, T, ignore_periods, optimizer, observation_params)
+                    else:
+                        _, reported = self.run(data, T, ignore_periods, train=False, observation_params=observation_params)
+                    hist[which][epoch] += reported
+                    samples += data["demands"].shape[0]
+                if samples == 0:
+                    raise ValueError("SmallPolicyEnsemble.fit needs at least one training batch and one dev batch")
+                hist[which][epoch] /= float(samples * (T - ignore_periods) * n_stores)
+            if self.best_dev is None:
+                self.best_dev = torch.full((K,), float("inf"), device=dev)
+                self.best_weights = self.weights.clone()
+            better = hist[1][epoch] < self.best_dev
+            self.best_dev = torch.where(better, hist[1][epoch], self.best_dev)
+            self.best_weights = torch.where(better[:, None], self.weights, self.best_weights)
+        return hist[0], hist[1]
+
+    def load_best(self):
+        """bound parameters <- `best_weights` (the parameters after the epoch with each model's lowest dev loss)"""
+        if self.best_weights is None or not self._bound:
+            raise ValueError("SmallPolicyEnsemble.load_best: no fit() has run on bound parameters")
+        self.weights.copy_(self.best_weights)
