@@ -422,6 +422,35 @@ int nic_small_rollout_ensemble_reduce(const NicSmallEnsemble* e, const float* sl
                                       float* grad, const float* rewards, int64_t n_reward_elems, int64_t ignore_elems, float* totals,
                                       float* scratch, void* stream);
 
+/* ---- K small policies on I problem instances: the same launch pair, each model reading ITS instance's inputs -------------------
+ * The K models are I instances x R = K / I replicas (I divides K): model m runs on instance m / R (grid z = instance, grid y =
+ * replica).  An instance is a demand trace, an initial state and the eight static tables; instance i's copy of each starts
+ * i * stride floats behind instance 0's, which is what the descriptor points at (pointers and tables alike).  Stride 0 = shared by
+ * all instances; all strides 0 is nic_small_rollout_ensemble_* exactly.  Everything else of the descriptor - B, ldb, T, t0, the
+ * pipeline shape (Ws / Wn / Ww / E / We: lead times may differ per instance within it), the head, the flags, upper_bound - and
+ * g_reward are shared.  Every model's numbers are the bits of a single-model call on its weights and its instance's inputs.
+ * The checks are csrc/small_ensemble_plan.h's (small_instances_check): 1 <= n_instances <= 65535 dividing n_models, R <= 65535, no
+ * negative stride, a non-zero demand stride >= (t0 + T) * ldb, a non-zero state0 stride >= F * ldb, both multiples of 4 floats, no
+ * stride for a table whose pointer is NULL.  A refused request returns non-zero, leaves a message in nic_last_error and launches
+ * nothing.  The reduction is per model already: nic_small_rollout_ensemble_reduce as it is. */
+typedef struct NicSmallInstances {
+    int32_t n_instances, reserved;
+    int64_t demand, state0;                /* traces [I][>= (t0 + T) * ldb], initial states [I][>= F * ldb] */
+    int64_t underage, holding, lead;       /* the tables, in the descriptor's order */
+    int64_t wh_holding, wh_lead, wh_edge;
+    int64_t ech_holding, ech_lead;
+} NicSmallInstances;
+/* K forward rollouts on I instances in one launch (trainer.py:181-216, `simulate_batch`, once per model and setting); buffers as
+ * nic_small_rollout_ensemble_fwd. */
+int nic_small_rollout_instances_fwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst,
+                                    float* rewards, float* state_final, float* states_hist, float* hidden_hist,
+                                    float* logits_hist, void* stream);
+/* K backward sweeps with in-kernel weight gradients on I instances in one launch (trainer.py:181-216 under `backward`,
+ * trainer.py:173, once per model and setting); buffers as nic_small_rollout_ensemble_bwd_wgrad. */
+int nic_small_rollout_instances_bwd_wgrad(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst,
+                                          const float* states_hist, const float* hidden_hist, const float* logits_hist,
+                                          NicTable2 g_reward, float* slab, int64_t slab_row_stride, void* stream);
+
 /* ---- Adam for K models whose parameters are rows of one buffer: two launches per step for all of them -------------------------
  * Replaces main_run.py:110 (`torch.optim.Adam(model.parameters(), lr=...)`) stepped by trainer.py:177 (`optimizer.step()`), once per
  * model (K optimizers, or K parameter groups: torch launches per group).  Row m of params / grads / exp_avg / exp_avg_sq starts

@@ -84,6 +84,16 @@ class NicSmallEnsembleSlices(C.Structure):
                                          "slab_row_stride", "slab", "grad", "scratch")]
 
 
+INSTANCE_TABLES = ("underage", "holding", "lead", "wh_holding", "wh_lead", "wh_edge", "ech_holding", "ech_lead")
+
+
+class NicSmallInstances(C.Structure):
+    """I problem instances under one ensemble launch: floats between two instances' demand traces, initial states and tables
+    (0: shared; include/nic_rollout.h)"""
+    _fields_ = ([("n_instances", C.c_int32), ("reserved", C.c_int32)]
+                + [(n, C.c_int64) for n in ("demand", "state0") + INSTANCE_TABLES])
+
+
 class NicEnsembleAdamState(C.Structure):
     """one model's Adam state on the device: steps taken, beta1^step and beta2^step as running products (include/nic_rollout.h)"""
     _fields_ = [("step", C.c_int32), ("reserved", C.c_int32), ("c1", C.c_double), ("c2", C.c_double)]
@@ -216,6 +226,10 @@ PROTOTYPES = {
     "nic_small_rollout_ensemble_bwd_wgrad": (C.c_int, [C.POINTER(NicSmallRolloutDesc), C.POINTER(NicSmallEnsemble), _vp, _vp, _vp, NicTable2,
                                                        _vp, _i64, _vp]),
     "nic_small_rollout_ensemble_reduce": (C.c_int, [C.POINTER(NicSmallEnsemble), _vp, _i32, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "nic_small_rollout_instances_fwd": (C.c_int, [C.POINTER(NicSmallRolloutDesc), C.POINTER(NicSmallEnsemble), C.POINTER(NicSmallInstances),
+                                                  _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nic_small_rollout_instances_bwd_wgrad": (C.c_int, [C.POINTER(NicSmallRolloutDesc), C.POINTER(NicSmallEnsemble),
+                                                        C.POINTER(NicSmallInstances), _vp, _vp, _vp, NicTable2, _vp, _i64, _vp]),
     "nic_ensemble_adam_prepare": (C.c_int, [_i32, _vp, _vp, _vp, _vp]),
     "nic_ensemble_adam_update": (C.c_int, [_i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "nic_horizon_rollout_ok": (C.c_int, [C.POINTER(NicHorizonDesc)]),

@@ -127,4 +127,76 @@ NIC_SE_FN int small_ensemble_check_reduce(const NicSmallEnsemble& e, bool with_s
     return SE_OK;
 }
 
+// ---- I problem instances (nic_small_rollout_instances_*) --------------------------------------------------------------------------
+// The K models are I instances x R replicas: model m (grid y, as in every ensemble launch) reads instance m / R's demand trace,
+// initial state and tables, each `instance x stride` floats behind instance 0's (stride 0: shared).  The kernels get m / R from one
+// scalar multiply and shift by a constant the launcher computes: for m, R < 2^16, (m * ceil(2^32 / R)) >> 32 == m / R exactly (the
+// constant times R exceeds 2^32 by less than R <= 2^16, so the product's error stays below one unit of the quotient).
+// DECISION: the instance is NOT a third grid dimension.  Enabling the workgroup-id-z register moved the register allocation of the
+// serial 32-scenario forward from 188 to 206 VGPRs (two wavefronts per SIMD -> one) although the value is dead after entry; the
+// multiply-shift leaves every compiled-in instantiation at its registers (DESIGN.md records the figures).
+constexpr int kSiTables = 8;   // underage, holding, lead, wh_holding, wh_lead, wh_edge, ech_holding, ech_lead (the descriptor's order)
+NIC_SE_FN int small_instance_replicas(int n_models, int n_instances) { return n_models / n_instances; }
+NIC_SE_FN uint64_t small_instance_magic(int replicas) { return ((1ull << 32) + (uint64_t)replicas - 1) / (uint64_t)replicas; }
+NIC_SE_FN uint32_t small_instance_of(uint32_t model, uint64_t magic) { return (uint32_t)(((uint64_t)model * magic) >> 32); }
+NIC_SE_FN int64_t small_instance_offset(uint32_t instance, int64_t stride) { return (int64_t)instance * stride; }
+NIC_SE_FN NicSmallInstances small_instances_shared() { return NicSmallInstances{1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; }
+// table k's stride / the descriptor's table k
+NIC_SE_FN int64_t small_instance_table_stride(const NicSmallInstances& in, int k) {
+    const int64_t s[kSiTables] = {in.underage, in.holding, in.lead, in.wh_holding, in.wh_lead, in.wh_edge, in.ech_holding, in.ech_lead};
+    return s[k];
+}
+NIC_SE_FN const float* small_instance_table_ptr(const NicSmallRolloutDesc& d, int k) {
+    const float* p[kSiTables] = {d.underage.p, d.holding.p, d.lead.p, d.wh_holding.p, d.wh_lead.p, d.wh_edge.p, d.ech_holding.p, d.ech_lead.p};
+    return p[k];
+}
+NIC_SE_FN const char* small_instance_table_name(int k) {
+    const char* n[kSiTables] = {"underage", "holding", "lead", "wh_holding", "wh_lead", "wh_edge", "ech_holding", "ech_lead"};
+    return n[k];
+}
+// the descriptor's eight tables <- instance `instance`'s (a NULL table has stride 0: it stays NULL)
+NIC_SE_FN void small_instance_tables(NicSmallRolloutDesc& d, const NicSmallInstances& in, uint32_t instance) {
+    d.underage.p += small_instance_offset(instance, in.underage);
+    d.holding.p += small_instance_offset(instance, in.holding);
+    d.lead.p += small_instance_offset(instance, in.lead);
+    d.wh_holding.p += small_instance_offset(instance, in.wh_holding);
+    d.wh_lead.p += small_instance_offset(instance, in.wh_lead);
+    d.wh_edge.p += small_instance_offset(instance, in.wh_edge);
+    d.ech_holding.p += small_instance_offset(instance, in.ech_holding);
+    d.ech_lead.p += small_instance_offset(instance, in.ech_lead);
+}
+
+enum SmallInstancesRefusal {
+    SI_OK = 0, SI_COUNT, SI_DIVIDE, SI_GRID, SI_NEGATIVE, SI_DEMAND, SI_STATE0, SI_ALIGN, SI_NULL_TABLE,
+};
+NIC_SE_FN const char* small_instances_reason(int r) {
+    switch (r) {
+        case SI_OK: return "accepted";
+        case SI_COUNT: return "n_instances must be at least 1";
+        case SI_DIVIDE: return "n_instances must divide n_models";
+        case SI_GRID: return "n_instances and the replicas per instance must be at most 65535";
+        case SI_NEGATIVE: return "negative instance stride";
+        case SI_DEMAND: return "demand stride shorter than (t0 + T) * ldb";
+        case SI_STATE0: return "state0 stride shorter than F * ldb";
+        case SI_ALIGN: return "the strides of demand and state0 must be multiples of 4 floats";
+        case SI_NULL_TABLE: return "instance stride for a table whose pointer is NULL";
+        default: return "?";
+    }
+}
+// `d`: the request's descriptor (t0, T, ldb, F and which tables it has)
+NIC_SE_FN int small_instances_check(const NicSmallInstances& in, int n_models, const NicSmallRolloutDesc& d) {
+    if (in.n_instances < 1) return SI_COUNT;
+    if (n_models % in.n_instances != 0) return SI_DIVIDE;
+    if (in.n_instances > kSeMaxModels || small_instance_replicas(n_models, in.n_instances) > kSeMaxModels) return SI_GRID;
+    if (in.demand < 0 || in.state0 < 0) return SI_NEGATIVE;
+    for (int k = 0; k < kSiTables; ++k)
+        if (small_instance_table_stride(in, k) < 0) return SI_NEGATIVE;
+    if (in.demand != 0 && in.demand < ((int64_t)d.t0 + d.T) * d.ldb) return SI_DEMAND;
+    if (in.state0 != 0 && in.state0 < (int64_t)d.F * d.ldb) return SI_STATE0;
+    if (in.demand % 4 != 0 || in.state0 % 4 != 0) return SI_ALIGN;
+    for (int k = 0; k < kSiTables; ++k)
+        if (small_instance_table_stride(in, k) != 0 && small_instance_table_ptr(d, k) == nullptr) return SI_NULL_TABLE;
+    return SI_OK;
+}
+
 }  // namespace nic

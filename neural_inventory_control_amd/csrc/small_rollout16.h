@@ -6,6 +6,7 @@
 
 #include "../../include/nic_rollout.h"
 #include "nic_common.h"
+#include "small_ensemble_plan.h"
 #include "small_rollout_variants.h"
 
 namespace nic {
@@ -13,11 +14,31 @@ namespace nic {
 // accesses (n_out = 1: one float, no padding)
 __host__ __device__ inline int sr16_state_rows(int F) { return (F + 3) & ~3; }
 __host__ __device__ inline int sr16_logit_rows(int n_out) { return n_out == 1 ? 1 : (n_out + 3) & ~3; }
-// records the kernel name of a launch (small_rollout_variants.h words it); e: nullptr = one model
-inline void sr_note_kernel(SrRoute route, const NicSmallRolloutDesc& d, int shape, const NicSmallEnsemble* e) {
+// records the kernel name of a launch (small_rollout_variants.h words it); e: nullptr = one model; inst: nullptr = not one of the
+// nic_small_rollout_instances_* entry points
+inline void sr_note_kernel(SrRoute route, const NicSmallRolloutDesc& d, int shape, const NicSmallEnsemble* e,
+                           const NicSmallInstances* inst = nullptr) {
     char name[160];
-    sr_kernel_name(name, sizeof(name), route, sr_lane_width(d), d.n_hidden, shape, e ? e->n_models : 0);
+    sr_kernel_name(name, sizeof(name), route, sr_lane_width(d), d.n_hidden, shape, e ? e->n_models : 0, inst ? inst->n_instances : 0);
     note_kernelf("%s", name);
+}
+// What the ensemble instantiations take besides the single-model arguments: the per-model strides (Sr*Strides below) and the
+// per-instance ones (all zero unless the launch came through nic_small_rollout_instances_*).  The single-model instantiations keep
+// the per-model struct alone, which they do not read.
+template <class PerModel>
+struct SrWithInstances : PerModel {
+    NicSmallInstances inst;
+    uint64_t magic;   // small_instance_magic(models per instance): instance = small_instance_of(model, magic)
+};
+template <class PerModel, bool ENS>
+using SrKernelStrides = std::conditional_t<ENS, SrWithInstances<PerModel>, PerModel>;
+template <class PerModel>
+inline SrWithInstances<PerModel> sr_with_instances(const PerModel& es, const NicSmallEnsemble* e, const NicSmallInstances* inst) {
+    SrWithInstances<PerModel> out;
+    static_cast<PerModel&>(out) = es;
+    out.inst = inst ? *inst : small_instances_shared();
+    out.magic = small_instance_magic(e ? small_instance_replicas(e->n_models, out.inst.n_instances) : 1);
+    return out;
 }
 // what the ensemble instantiations of the kernels take of a NicSmallEnsemble: floats between two models' slices of the buffers
 // that kernel touches (the forward's history strides are zero when the histories are NULL: NULL + m x 0 stays NULL)
@@ -31,11 +52,12 @@ inline SrFwdStrides sr_fwd_strides(const NicSmallEnsemble* e, bool with_history)
 inline SrBwdStrides sr_bwd_strides(const NicSmallEnsemble* e) {
     return e ? SrBwdStrides{e->weights, e->states, e->hidden, e->logits, e->slab} : SrBwdStrides{0, 0, 0, 0, 0};
 }
-// e: nullptr = one model (the single-model instantiations), else K models, one grid row each (nic_small_rollout_ensemble_*);
-// false: no kernel for this n_hidden, nothing was launched
+// e: nullptr = one model (the single-model instantiations), else K models, one grid row each (nic_small_rollout_ensemble_*), on
+// inst's problem instances (nullptr: one, shared); false: no kernel for this n_hidden, nothing was launched
 bool small_rollout16_fwd(const NicSmallRolloutDesc& d, int shape, float* rewards, float* state_final, float* states_hist,
-                         float* hidden_hist, float* logits_hist, hipStream_t s, const NicSmallEnsemble* e = nullptr);
+                         float* hidden_hist, float* logits_hist, hipStream_t s, const NicSmallEnsemble* e = nullptr,
+                         const NicSmallInstances* inst = nullptr);
 bool small_rollout16_bwd_wgrad(const NicSmallRolloutDesc& d, int shape, const float* states_hist, const float* hidden_hist,
                                const float* logits_hist, NicTable2 g_reward, float* slab, int64_t slab_stride, hipStream_t s,
-                               const NicSmallEnsemble* e = nullptr);
+                               const NicSmallEnsemble* e = nullptr, const NicSmallInstances* inst = nullptr);
 }  // namespace nic

@@ -70,9 +70,10 @@ __device__ __forceinline__ void layer32(const float (&aW)[2][8], const float (&b
     }
 }
 
-// ENS: K models of one architecture on one batch, model m = blockIdx.y on its own slice of every per-model buffer (m x the stride
-// of `es`, single-model layout inside a slice; demand, state0 and the tables are shared).  The offsets are wave-uniform - scalar
-// arithmetic on the kernel arguments before the first load - and nothing in the period loop knows of them.  ENS = false is the
+// ENS: K models of one architecture in one launch, model m = blockIdx.y on its
+// own slice of every per-model buffer (m x the stride of `es`, single-model layout inside a slice) and on its instance's demand,
+// state0 and tables (instance = m / replicas x the stride of `es.inst`; all zero: shared - csrc/small_ensemble_plan.h).  The offsets are
+// wave-uniform - scalar arithmetic on the kernel arguments before the first load - and nothing in the period loop knows of them.  ENS = false is the
 // single-model kernel as it was (`es` is not read).
 template <int NL, int SHAPE, bool ENS>
 __global__ __launch_bounds__(64, 2) void small_rollout16_fwd_kernel(NicSmallRolloutDesc d, const float* __restrict__ weights,
@@ -80,10 +81,14 @@ __global__ __launch_bounds__(64, 2) void small_rollout16_fwd_kernel(NicSmallRoll
                                                                     const float* __restrict__ state0, float* __restrict__ rewards,
                                                                     float* __restrict__ state_final, float* __restrict__ states_hist,
                                                                     float* __restrict__ hidden_hist, float* __restrict__ logits_hist,
-                                                                    nic::SrFwdStrides es) {
+                                                                    nic::SrKernelStrides<nic::SrFwdStrides, ENS> es) {
     using namespace nic;
     if constexpr (ENS) {
         const int64_t m = blockIdx.y;
+        const uint32_t inst = small_instance_of(blockIdx.y, es.magic);
+        demand += small_instance_offset(inst, es.inst.demand);
+        state0 += small_instance_offset(inst, es.inst.state0);
+        small_instance_tables(d, es.inst, inst);
         weights += m * es.weights;
         rewards += m * es.rewards;
         state_final += m * es.final_state;
@@ -223,10 +228,13 @@ __global__ __launch_bounds__(64, 2) void small_rollout16_bwd_kernel(NicSmallRoll
                                                                  const float* __restrict__ states_hist,
                                                                  const float* __restrict__ hidden_hist,
                                                                  const float* __restrict__ logits_hist, NicTable2 g_reward,
-                                                                 float* __restrict__ slab, int64_t slab_stride, nic::SrBwdStrides es) {
+                                                                 float* __restrict__ slab, int64_t slab_stride, nic::SrKernelStrides<nic::SrBwdStrides, ENS> es) {
     using namespace nic;
-    if constexpr (ENS) {   // (model m = blockIdx.y on its own slices, see the forward kernel; g_reward is shared)
+    if constexpr (ENS) {   // (model m on its own slices and its instance's inputs, see the forward kernel; g_reward is shared)
         const int64_t m = blockIdx.y;
+        const uint32_t inst = small_instance_of(blockIdx.y, es.magic);
+        demand += small_instance_offset(inst, es.inst.demand);
+        small_instance_tables(d, es.inst, inst);
         weights += m * es.weights;
         states_hist += m * es.states;
         hidden_hist += m * es.hidden;
@@ -506,12 +514,13 @@ extern "C" int nic_tuning_set_small_rollout_stamps(void* buf) {   // buf: device
 
 namespace nic {
 
-// e == nullptr: the single-model kernels (grid y = 1, no strides); else the ensemble instantiations, one grid row per model
+// e == nullptr: the single-model kernels (grid y = 1, no strides); else the ensemble instantiations, one grid row per model, on
+// inst's problem instances (nullptr: one, shared)
 bool small_rollout16_fwd(const NicSmallRolloutDesc& d, int shape, float* rewards, float* state_final, float* states_hist,
-                         float* hidden_hist, float* logits_hist, hipStream_t s, const NicSmallEnsemble* e) {
+                         float* hidden_hist, float* logits_hist, hipStream_t s, const NicSmallEnsemble* e, const NicSmallInstances* inst) {
     const dim3 grid(nic::ceil_div(d.n_scenarios, 16), e ? e->n_models : 1), block(64);
-    const nic::SrFwdStrides es = nic::sr_fwd_strides(e, states_hist != nullptr);   // (the kernels add m x stride unconditionally)
-    sr_note_kernel(SR_FWD, d, shape, e);
+    const auto es = sr_with_instances(sr_fwd_strides(e, states_hist != nullptr), e, inst);   // (the kernels add m x stride unconditionally)
+    sr_note_kernel(SR_FWD, d, shape, e, inst);
     return sr_dispatch<SR_FWD>(sr_variant(SR_FWD, shape, d.n_hidden), e != nullptr, [&](auto nl, auto sh, auto ens) {
         hipLaunchKernelGGL((small_rollout16_fwd_kernel<nl(), sh(), ens()>), grid, block, 0, s, d, d.weights, d.demand, d.state0, rewards,
                            state_final, states_hist, hidden_hist, logits_hist, es);
@@ -520,10 +529,10 @@ bool small_rollout16_fwd(const NicSmallRolloutDesc& d, int shape, float* rewards
 
 bool small_rollout16_bwd_wgrad(const NicSmallRolloutDesc& d, int shape, const float* states_hist, const float* hidden_hist,
                                const float* logits_hist, NicTable2 g_reward, float* slab, int64_t slab_stride, hipStream_t s,
-                               const NicSmallEnsemble* e) {
+                               const NicSmallEnsemble* e, const NicSmallInstances* inst) {
     const dim3 grid(nic::ceil_div(d.n_scenarios, 16), e ? e->n_models : 1), block(64);
-    const nic::SrBwdStrides es = nic::sr_bwd_strides(e);
-    sr_note_kernel(SR_BWD_WGRAD, d, shape, e);
+    const auto es = sr_with_instances(sr_bwd_strides(e), e, inst);
+    sr_note_kernel(SR_BWD_WGRAD, d, shape, e, inst);
     return sr_dispatch<SR_BWD_WGRAD>(sr_variant(SR_BWD_WGRAD, shape, d.n_hidden), e != nullptr, [&](auto nl, auto sh, auto ens) {
         hipLaunchKernelGGL((small_rollout16_bwd_kernel<nl(), sh(), ens()>), grid, block, 0, s, d, d.weights, d.demand, states_hist,
                            hidden_hist, logits_hist, g_reward, slab, slab_stride, es);

@@ -43,13 +43,16 @@ constexpr SrVariant sr_variant(SrRoute route, int shape, int n_hidden) {
 }
 
 // The recorded kernel name (nic_last_kernel()).  It states the REQUEST - width, n_hidden, the chain's shape class, the models of an
-// ensemble launch (n_models 0: the single-model entry points) -, so the two dz-history cells without a kernel of their own are
-// recorded under their shape's name.
-inline void sr_kernel_name(char* out, size_t size, SrRoute route, int width, int n_hidden, int shape, int n_models) {
+// ensemble launch (n_models 0: the single-model entry points), the instances of a launch through nic_small_rollout_instances_*
+// (n_instances 0: every other entry point) -, so the two dz-history cells without a kernel of their own are recorded under their
+// shape's name.
+inline void sr_kernel_name(char* out, size_t size, SrRoute route, int width, int n_hidden, int shape, int n_models, int n_instances = 0) {
     const char* kernel = route == SR_FWD ? (width == 16 ? "small_rollout16_fwd_kernel" : "small_rollout_fwd_mfma_kernel")
                                          : (width == 16 ? "small_rollout16_bwd_kernel" : "small_rollout_bwd_mfma_kernel");
     const char* wgrad = route == SR_BWD_WGRAD ? "wgrad," : "";
-    if (n_models > 0) snprintf(out, size, "%s<%d,%s%s,models=%d>", kernel, n_hidden, wgrad, sr_shape_name(shape), n_models);
+    if (n_models > 0 && n_instances > 0)
+        snprintf(out, size, "%s<%d,%s%s,models=%d,instances=%d>", kernel, n_hidden, wgrad, sr_shape_name(shape), n_models, n_instances);
+    else if (n_models > 0) snprintf(out, size, "%s<%d,%s%s,models=%d>", kernel, n_hidden, wgrad, sr_shape_name(shape), n_models);
     else snprintf(out, size, "%s<%d,%s%s>", kernel, n_hidden, wgrad, sr_shape_name(shape));
 }
 

@@ -13,15 +13,27 @@ packs all K models' weights again every call.  The whole training step is `train
 then the bias), so nothing is packed, and an `EnsembleAdam` (ensemble_adam.py) updates all K rows with two launches - six
 launches a step (forward, backward, two of the reduction, prepare, update) and no per-model Python.  `use_graph` replays them from
 one captured sequence per batch shape (launch_replay.py); `fit` is the epoch loop over `train_step` with the best weights per
-model kept on the device.  YAML / `main_run` wiring, a `torch.library` operator and multi-GPU sharding are not part of this engine.
+model kept on the device.
+
+The K models need not share the batch: `run`, `train_step` and `fit` take a list (or tuple) of I batch dicts in place of one, I
+dividing K, and model m then runs on instance m // (K // I) - its own demand trace, initial state and cost / lead-time tables
+(`nic_small_rollout_instances_*`: the same launch pair, every model reading its instance's inputs).  That is the reference's
+hyper-parameter grid over a setting (one_store_lost.yml: underage_cost 4, 9, 19, 39) x seeds in one engine.  The instances share B,
+the trace length, the pipeline shape (lead times may differ within it) and the flags; `check_instances` names the first mismatch.
+The engine owns the instance-stacked inputs per batch shape (demand [I][T_total][1][ldb], state0 [I][F][ldb], one stacked tensor
+per table) at fixed addresses, so a replayed step stages and pins nothing.  A plain dict is the one-batch path, unchanged.
+
+YAML / `main_run` wiring, a `torch.library` operator and multi-GPU sharding are not part of this engine.
 """
+import copy
+
 import torch
 
 from . import _lib
 from . import small_rollout as sr
 from .ensemble_adam import EnsembleAdam
 from .launch_replay import LaunchReplay, ReplayedEngine
-from .layout import demand_trace_soa, Table
+from .layout import demand_trace_soa, EnvProblem, Table
 from .rollout import _HEADS, FusedRollout
 
 SMALL_POLICIES = ("vanilla_one_store", "vanilla_serial")
@@ -61,6 +73,55 @@ def check_models(models):
     return models
 
 
+def check_instances(probs, n_models, trace_lengths=None):
+    """The problem instances one launch pair takes: I >= 1 `EnvProblem`s, I dividing the K models, that agree in everything the
+    kernels take once - B, the pipeline shape, the flags, the trace length (`trace_lengths`, one per instance, if given) and every
+    table's layout (present or not, uniform or per-scenario: one descriptor addresses all instances).  ValueError names the first
+    mismatch.  Host-side only.  Returns the replicas per instance."""
+    probs = list(probs)
+    I = len(probs)
+    if I < 1:
+        raise ValueError("SmallPolicyEnsemble needs at least one problem instance")
+    if n_models % I != 0:
+        raise ValueError(f"SmallPolicyEnsemble: {I} problem instances do not divide {n_models} models")
+    first = probs[0]
+    for i, p in enumerate(probs[1:], 1):
+        if p.B != first.B:
+            raise ValueError(f"instance {i}: {p.B} scenarios, instance 0 has {first.B}")
+        if trace_lengths is not None and trace_lengths[i] != trace_lengths[0]:
+            raise ValueError(f"instance {i}: a demand trace of {trace_lengths[i]} periods, instance 0's has {trace_lengths[0]}")
+        shape = lambda q: (q.S, q.Wn, q.E, q.Ws, q.Ww, q.We)  # noqa: E731
+        if shape(p) != shape(first):
+            raise ValueError(f"instance {i}: pipeline shape (S, Wn, E, Ws, Ww, We) = {shape(p)} differs from instance 0's {shape(first)}")
+        if (p.lost_demand, p.maximize_profit) != (first.lost_demand, first.maximize_profit):
+            raise ValueError(f"instance {i}: lost_demand / maximize_profit differ from instance 0's")
+        for name in EnvProblem._TABLES:
+            a, b = getattr(first, name), getattr(p, name)
+            if (a.tensor is None) != (b.tensor is None):
+                raise ValueError(f"instance {i}: table {name!r} is {'missing' if b.tensor is None else 'present'}, instance 0's is not")
+            if a.tensor is not None and (a.scn_stride == 0) != (b.scn_stride == 0):
+                kind = lambda t: "uniform" if t.scn_stride == 0 else "per-scenario"  # noqa: E731
+                raise ValueError(f"instance {i}: table {name!r} is {kind(b)}, instance 0's is {kind(a)}")
+            if a.tensor is not None and ((tuple(a.tensor.shape), a.loc_stride, a.sup_stride)
+                                         != (tuple(b.tensor.shape), b.loc_stride, b.sup_stride)):
+                raise ValueError(f"instance {i}: table {name!r} has shape {tuple(b.tensor.shape)}, instance 0's {tuple(a.tensor.shape)}")
+    return n_models // I
+
+
+def stack_instance_tables(probs):
+    """An `EnvProblem` like probs[0] whose tables are [I][...] stacks of the instances' (instance 0 first: a descriptor built from it
+    points at instance 0, instance i's copy of a table starts i x the returned stride behind) and {table: stride in floats}."""
+    stacked, strides = copy.copy(probs[0]), {}
+    for name in EnvProblem._TABLES:
+        t = getattr(probs[0], name)
+        if t.tensor is None:
+            continue
+        tensor = torch.stack([getattr(p, name).tensor.contiguous() for p in probs])
+        setattr(stacked, name, Table(tensor, t.loc_stride, t.scn_stride, t.sup_stride))
+        strides[name] = tensor[0].numel()
+    return stacked, strides
+
+
 def pack_ensemble_weights(linears_per_model, out=None):
     """[K][P]: row m = `pack_weights` of model m's layers, all K models in ONE torch.cat (one launch)."""
     K = len(linears_per_model)
@@ -82,7 +143,10 @@ class _ShapeState:
     their addresses, its staged demand trace and its pinned problem.  Weights, gradients and optimizer state depend on (K, P)
     only and are the engine's."""
     FIELDS = ("plan", "state0", "rewards", "final", "totals", "slices", "scratch", "strides", "ens", "states", "hidden", "logits", "slab",
-              "g_reward", "g_reward_key")
+              "g_reward", "g_reward_key",
+              # I problem instances: the stacked inputs (demand [I][T_total][1][ldb], state0 [I][F][ldb], the problem whose tables are
+              # [I][...]), the NicSmallInstances strides and the instances' problems the tables were last copied from
+              "inst_demand", "inst_state0", "inst_prob", "inst", "inst_sources")
 
     def __init__(self, use_graph):
         for name in self.FIELDS:
@@ -196,9 +260,10 @@ class SmallPolicyEnsemble(ReplayedEngine):
             self._shapes.pop(next(iter(self._shapes)))
         self._key = key
 
-    def _setup(self, prob, T, train):
+    def _setup(self, prob, T, train, instances=()):
         """Sizes what this batch needs; returns the models' layers (None once the parameters are bound: nothing is packed, and the
-        per-model checks were made when they were bound)."""
+        per-model checks were made when they were bound).  `instances`: what the key of a list-of-instances batch carries besides
+        the shape (I, the trace length, the tables' layouts); a one-batch run has none."""
         K, dev, ld = self.n_models, self.device, prob.ldb
         F = prob.S * prob.Ws + (0 if self.head == "softplus" else prob.Wn * prob.Ww + prob.E * prob.We)
         if self._bound:
@@ -214,7 +279,7 @@ class SmallPolicyEnsemble(ReplayedEngine):
             if self._bind_requested:
                 self._bind(lins, dims)
                 lins = None
-        key = (prob.B, T, K, tuple(dims), prob.Ws, prob.Wn, prob.Ww, prob.E, prob.We)
+        key = (prob.B, T, K, tuple(dims), prob.Ws, prob.Wn, prob.Ww, prob.E, prob.We) + tuple(instances)
         if self._key != key:
             self._switch_shape(key)
         sh = self._shape
@@ -261,7 +326,8 @@ class SmallPolicyEnsemble(ReplayedEngine):
     # ---- one batch ---------------------------------------------------------------------------------------------------------------
     def run(self, data, periods, ignore_periods=0, train=True, observation_params=None, demand_soa=None, grad_scale=None,
             accumulate_grads=False, discrete_allocation=False):
-        """Rollout of one batch under every model (and, if `train`, d(mean loss)/d(theta) into every model's `param.grad`: views
+        """Rollout of one batch - or, `data` a list of I batches, of instance m // (K // I)'s batch - under every model (and, if
+        `train`, d(mean loss)/d(theta) into every model's `param.grad`: views
         into one [K][P] gradient buffer, `accumulate_grads` adds - `small_rollout.assign_grads`).  Arguments as
         `FusedRollout.run`.  Returns (total [K], reported [K]) device tensors; `rewards` [K][T][ldb] holds the per-period costs."""
         if discrete_allocation and train:
@@ -272,7 +338,8 @@ class SmallPolicyEnsemble(ReplayedEngine):
         return tt[:, 0], tt[:, 1]
 
     def train_step(self, data, periods, ignore_periods=0, optimizer=None, observation_params=None, demand_soa=None, grad_scale=None):
-        """One whole training step of all K models: forward, backward, the reduction's two launches and `optimizer`'s two (an
+        """One whole training step of all K models (on one batch, or on a list of I instances' batches as in `run`): forward,
+        backward, the reduction's two launches and `optimizer`'s two (an
         `EnsembleAdam` over this engine's (K, P)) - no packing, no `param.grad`, no per-model Python.  Needs `bind_parameters()`.
         Returns (total [K], reported [K]) of the step BEFORE the update, as `run` does."""
         if not self._bind_requested:
@@ -282,7 +349,22 @@ class SmallPolicyEnsemble(ReplayedEngine):
         tt = self._step(data, periods, ignore_periods, True, observation_params, demand_soa, grad_scale, False, optimizer)
         return tt[:, 0], tt[:, 1]
 
+    def _fill_state0(self, state0, prob, data):
+        """state0 [F][ldb] <- the batch's initial pipelines in the reference's cat(flatten(...)) order"""
+        B = prob.B
+        a, b = prob.S * prob.Ws, prob.S * prob.Ws + prob.Wn * prob.Ww
+        state0[:a].view(prob.S, prob.Ws, -1)[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
+        if self.head != "softplus":
+            if prob.Wn:
+                state0[a:b].view(prob.Wn, prob.Ww, -1)[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
+            if prob.E:
+                state0[b:b + prob.E * prob.We].view(prob.E, prob.We, -1)[:, :, :B].copy_(
+                    data["initial_echelon_inventories"].permute(1, 2, 0))
+
     def _step(self, data, periods, ignore_periods, train, observation_params, demand_soa, grad_scale, discrete_allocation, optimizer):
+        if isinstance(data, (list, tuple)):
+            return self._step_instances(data, periods, ignore_periods, train, observation_params, demand_soa, grad_scale,
+                                        discrete_allocation, optimizer)
         lead, dev, K = self._engines[0], self.device, self.n_models
         prob = lead._problem_for(data)
         T, B, ld = periods, prob.B, prob.ldb
@@ -302,14 +384,7 @@ class SmallPolicyEnsemble(ReplayedEngine):
         demand_soa = replay.stage_demand(demand_soa)
         if not self._bound:
             pack_ensemble_weights(lins, self.weights)   # (every run: the optimizers moved the parameters)
-        a, b = prob.S * prob.Ws, prob.S * prob.Ws + prob.Wn * prob.Ww
-        sh.state0[:a].view(prob.S, prob.Ws, -1)[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
-        if self.head != "softplus":
-            if prob.Wn:
-                sh.state0[a:b].view(prob.Wn, prob.Ww, -1)[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
-            if prob.E:
-                sh.state0[b:b + prob.E * prob.We].view(prob.E, prob.We, -1)[:, :, :B].copy_(
-                    data["initial_echelon_inventories"].permute(1, 2, 0))
+        self._fill_state0(sh.state0, prob, data)
         ub = lead._ub() if self.head != "softplus" else 0.0
         width = sr.lane_width(self.small_lane_scenarios, train, B)
         desc = sh.plan.desc(T, shift, self.weights, demand_soa, sh.state0, ub, round_orders=discrete_allocation, prob=prob,
@@ -350,9 +425,98 @@ class SmallPolicyEnsemble(ReplayedEngine):
         replay.ran()
         return sh.totals.clone()   # (outside the capture: the caller's tensors must not change under a later step)
 
+    def _step_instances(self, datas, periods, ignore_periods, train, observation_params, demand_soa, grad_scale, discrete_allocation,
+                        optimizer):
+        """`_step` for a list of I batches: model m runs on datas[m // (K // I)].  The instances' inputs are copied into this batch
+        shape's stacked buffers (the tables only when the batches present other tensors than last time), whose addresses a captured
+        sequence keeps: nothing is pinned or staged."""
+        lead, dev, K = self._engines[0], self.device, self.n_models
+        I = len(datas)
+        if I < 1 or K % I != 0:   # (before anything is built from the batches)
+            raise ValueError(f"SmallPolicyEnsemble: {I} problem instances do not divide {K} models")
+        probs = [lead._problem_for(data) for data in datas]
+        lengths = [int(data["demands"].shape[2]) for data in datas]
+        check_instances(probs, K, lengths)
+        prob0 = probs[0]
+        T, B, ld, T_total = periods, prob0.B, prob0.ldb, lengths[0]
+        shift = observation_params["demand"]["period_shift"] if observation_params else 0
+        if T_total < T + shift:
+            raise ValueError("Current period is greater than the number of periods in the data")
+        if demand_soa is not None and tuple(demand_soa.shape) != (I, T_total, 1, ld):
+            raise ValueError(f"SmallPolicyEnsemble: demand_soa of a list of instances must be [I][T_total][1][ldb] = {(I, T_total, 1, ld)}, "
+                             f"got {tuple(demand_soa.shape)}")
+        layouts = tuple((name, getattr(prob0, name).scn_stride) for name in EnvProblem._TABLES if getattr(prob0, name).tensor is not None)
+        lins = self._setup(prob0, T, train, instances=("instances", I, T_total, layouts))
+        if optimizer is not None and (optimizer.n_models, optimizer.P) != tuple(self.weights.shape):
+            raise ValueError(f"SmallPolicyEnsemble.train_step: the optimizer is for {optimizer.n_models} models of {optimizer.P} parameters, "
+                             f"the engine has {K} of {self.weights.shape[1]}")
+        sh = self._shape
+        replay = sh.replay
+        F = sh.plan.F
+        if sh.inst_state0 is None:
+            sh.inst_state0 = torch.zeros(I, F, ld, device=dev)
+            sh.inst_prob, table_strides = stack_instance_tables(probs)
+            sh.inst_sources = probs
+            sh.inst = sr.instance_strides(I, state0=F * ld, demand=T_total * ld, **table_strides)
+        elif not all(a is b for a, b in zip(sh.inst_sources, probs)):
+            for name in EnvProblem._TABLES:   # (other batches than last time: their tables into the stacked ones, in place)
+                stacked = getattr(sh.inst_prob, name).tensor
+                if stacked is not None:
+                    for i, p in enumerate(probs):
+                        stacked[i].copy_(getattr(p, name).tensor)
+            sh.inst_sources = probs
+        if demand_soa is None:
+            if sh.inst_demand is None:
+                sh.inst_demand = torch.zeros(I, T_total, 1, ld, device=dev)
+            demand_soa = sh.inst_demand
+            for i, data in enumerate(datas):
+                demand_soa[i, :, :, :B].copy_(data["demands"].permute(2, 1, 0))
+        if not self._bound:
+            pack_ensemble_weights(lins, self.weights)   # (every run: the optimizers moved the parameters)
+        for i, data in enumerate(datas):
+            self._fill_state0(sh.inst_state0[i], prob0, data)
+        ub = lead._ub() if self.head != "softplus" else 0.0
+        width = sr.lane_width(self.small_lane_scenarios, train, B)
+        desc = sh.plan.desc(T, shift, self.weights, demand_soa, sh.inst_state0, ub, round_orders=discrete_allocation, prob=sh.inst_prob,
+                            lane_scenarios=width)
+        hist = (sh.states, sh.hidden, sh.logits) if train else (None, None, None)
+        n_el = T * ld
+        if train:
+            if grad_scale is None:
+                grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
+            sh.g_reward_key = sr.set_g_reward(sh.g_reward, B, grad_scale, sh.g_reward_key)
+
+        def launches():
+            sr.small_rollout_instances_fwd(desc, sh.ens, sh.inst, sh.rewards, sh.final, *hist)
+            self._note("fwd")
+            if train:
+                row = sh.slab.shape[2]
+                sr.small_rollout_instances_bwd_wgrad(desc, sh.ens, sh.inst, *hist, Table(sh.g_reward, 0, 1), sh.slab, row)
+                self._note("bwd")
+                sr.small_rollout_ensemble_reduce(sh.ens, sh.slab, sr.slab_rows_written(B, width), row, self.grad.shape[1], self.grad,
+                                                 sh.rewards, n_el, ignore_periods * ld, sh.totals, sh.scratch)
+            else:
+                sr.small_rollout_ensemble_reduce(sh.ens, None, 0, 0, 0, None, sh.rewards, n_el, ignore_periods * ld, sh.totals,
+                                                 sh.scratch)
+            self._note("reduce")
+            if optimizer is not None:
+                optimizer.step(self.weights, self.grad)
+
+        # (as in `_step`; a caller's demand_soa is read in place, so its address is part of the capture's key)
+        if replay.on():
+            replay.set_variant((K, I, self.small_lane_scenarios, self.weights.data_ptr(), ub))
+        opt_key = optimizer and tuple(t.data_ptr() for t in (optimizer.hyper, optimizer.state, optimizer.coef, optimizer.exp_avg,
+                                                               optimizer.exp_avg_sq))
+        replay.probe_begin(train)
+        replay.call((train, opt_key, ignore_periods, shift, bool(discrete_allocation), width, I, demand_soa.data_ptr()), launches)
+        replay.probe_end()
+        replay.ran()
+        return sh.totals.clone()
+
     # ---- epochs ------------------------------------------------------------------------------------------------------------------
     def fit(self, train_batches, dev_batches, epochs, periods, dev_periods, ignore_periods, optimizer, observation_params=None):
-        """`epochs` times: `train_step` over `train_batches`, then `run(train=False)` over `dev_batches`.  Returns the train and dev
+        """`epochs` times: `train_step` over `train_batches`, then `run(train=False)` over `dev_batches` (each batch a dict, or a list
+        of I instances' dicts; the sample count is per instance).  Returns the train and dev
         histories [epochs][K]: the reported cost per (scenario, reported period, store) as `Trainer.do_one_epoch` averages it.
         The best dev loss per model and the parameters that gave it are tracked on the device (`best_dev [K]`, `best_weights
         [K][P]`, updated with a mask): no host synchronisation inside an epoch.  `load_best()` puts them back."""
@@ -368,7 +532,7 @@ class SmallPolicyEnsemble(ReplayedEngine):
                     else:
                         _, reported = self.run(data, T, ignore_periods, train=False, observation_params=observation_params)
                     hist[which][epoch] += reported
-                    samples += data["demands"].shape[0]
+                    samples += (data[0] if isinstance(data, (list, tuple)) else data)["demands"].shape[0]   # (per instance)
                 if samples == 0:
                     raise ValueError("SmallPolicyEnsemble.fit needs at least one training batch and one dev batch")
                 hist[which][epoch] /= float(samples * (T - ignore_periods) * n_stores)

@@ -5,7 +5,7 @@ step per lane; a second kernel sweeps the horizon backwards and contracts the we
 wavefront), and `nic_small_rollout_reduce` sums those and the costs.  `nic_small_rollout_bwd`, the backward sweep that writes a dz
 history for one weight-gradient GEMM per layer, is kept as the referee of the in-kernel gradients.  Which kernel instantiation a
 request runs is decided in csrc/small_rollout_variants.h.  Used by `FusedRollout` when `SmallRolloutPlan.supports(...)` and by
-`SmallPolicyEnsemble`; the rules both engines follow around the launches (`lane_width`, `slab_rows_written`, `set_g_reward`,
+`SmallPolicyEnsemble` (K models in one launch pair, on one batch or on I problem instances); the rules both engines follow around the launches (`lane_width`, `slab_rows_written`, `set_g_reward`,
 `assign_grads`) are here.
 
 Descriptor building is pointer plumbing and device-agnostic (the CPU test build of the kernel bodies uses it too).
@@ -213,3 +213,33 @@ def small_rollout_ensemble_reduce(ens, slab, n_rows, slab_row_stride, P, grad, r
     _lib.check(_lib.lib().nic_small_rollout_ensemble_reduce(ens, _lib.ptr(slab), int(n_rows), int(slab_row_stride), int(P), _lib.ptr(grad),
                                                             _lib.ptr(rewards), int(n_reward_elems), int(ignore_elems),
                                                             _lib.ptr(totals), _lib.ptr(scratch), _lib.current_stream()))
+
+
+# ---- K models on I problem instances (nic_small_rollout_instances_*, csrc/small_ensemble_plan.h) -------------------------------------
+INSTANCE_FIELDS = tuple(n for n, _ in _lib.NicSmallInstances._fields_[2:])
+
+
+def instance_strides(n_instances, **strides):
+    """NicSmallInstances: floats between two instances' copies of the demand trace, the initial state and each of the eight tables
+    (what is not named: 0, shared by all instances).  Model m of K runs on instance m // (K // n_instances)."""
+    inst = _lib.NicSmallInstances()
+    inst.n_instances = int(n_instances)
+    for k, v in strides.items():
+        if k not in INSTANCE_FIELDS:
+            raise KeyError(k)
+        setattr(inst, k, int(v))
+    return inst
+
+
+def small_rollout_instances_fwd(desc, ens, inst, rewards, state_final, states_hist, hidden_hist, logits_hist):
+    """`small_rollout_ensemble_fwd` with every model on its instance's inputs; `desc` points at instance 0's."""
+    ops._dev(rewards)
+    _lib.check(_lib.lib().nic_small_rollout_instances_fwd(desc, ens, inst, _lib.ptr(rewards), _lib.ptr(state_final), _lib.ptr(states_hist),
+                                                          _lib.ptr(hidden_hist), _lib.ptr(logits_hist), _lib.current_stream()))
+
+
+def small_rollout_instances_bwd_wgrad(desc, ens, inst, states_hist, hidden_hist, logits_hist, g_reward: Table, slab, slab_row_stride):
+    ops._dev(slab)
+    _lib.check(_lib.lib().nic_small_rollout_instances_bwd_wgrad(desc, ens, inst, _lib.ptr(states_hist), _lib.ptr(hidden_hist),
+                                                                _lib.ptr(logits_hist), g_reward.t2(), _lib.ptr(slab),
+                                                                int(slab_row_stride), _lib.current_stream()))
