@@ -14,6 +14,7 @@ import torch
 import env_exact_cases as ex
 import kernel_checks as kc
 from golden_io import case_names
+from mlp3_checks import _mlp3_reference   # (the float64 formulation, shared with tests/test_gpu_mlp3.py)
 from neural_inventory_control_amd import _lib, ops
 from neural_inventory_control_amd.layout import pad_ld, to_soa
 
@@ -827,16 +828,6 @@ def test_sampler_poisson():
 
 
 # ---- fused 3-layer MLP over gathered inputs (csrc/mlp3.hip) ----------------------------------------------------------------
-
-def _mlp3_reference(x, W, act):
-    """x: (cols, K) float64; W: [(w1, b1), (w2, b2), (w3, b3)] float64 with requires_grad."""
-    import torch.nn.functional as F
-    h1 = F.elu(F.linear(x, *W[0]))
-    h2 = F.elu(F.linear(h1, *W[1]))
-    z = F.linear(h2, *W[2])
-    y = F.elu(z) if act == 1 else (F.softplus(z) if act == 2 else z)
-    return y, h1, h2
-
 
 @pytest.mark.parametrize("K_rows,n_out,act,B", [((32, 32, 1), 32, 1, 100), ((32, 32, 32), 32, 1, 64), ((7,), 32, 1, 37),
                                                  ((32,), 1, 2, 70), ((20, 13), 5, 0, 33)])
