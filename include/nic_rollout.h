@@ -585,6 +585,47 @@ int nic_horizon_rollout_bwd(const NicHorizonDesc* d, const float* state_hist, co
                             const float* logits_hist, const float* orders_hist, NicTable2 g_reward, float* dz1_hist,
                             float* dz2_hist, float* dz3_hist, void* stream);
 
+/* ---- K data_driven policies of ONE architecture on ONE batch: one forward and one backward whole-horizon launch for all of them ----
+ * A whole-horizon launch of the reference's real-data batch (72 products: 5 workgroups) leaves the device idle; a sweep over seeds,
+ * learning rates or initialisations of one architecture rides in the idle CUs.  Model m (grid y) runs the instruction stream of the
+ * single-model kernels above on its own W1 / W2 / W3 / b2 / b3 and z1_obs and writes its own rewards, final state, histories and dz
+ * buffers: model m's copy of each starts m * its stride floats behind model 0's, which is what the descriptor (weights) and the
+ * arguments (buffers) point at, and has exactly the single-model layout.  state0, the demand trace, the adjacency mask, the cost and
+ * lead-time tables, g_reward, hist_stride, T, t0 and the flags are shared.  Every model's numbers are the bits of a single-model
+ * call on its slice.  Only head_mode 0 (the MLP) has this form: a tape has no weights.
+ * Strides are in floats; csrc/horizon_ensemble_plan.h gives the slice sizes (nic_horizon_rollout_ensemble_slices) and the checks:
+ * 1 <= n_models <= 65535, no negative stride, every stride of a buffer that is passed >= its slice, the strides of z1_obs, the
+ * rewards, the final state, the histories and the dz buffers multiples of 4 floats (the GEMMs and the reduction that take a
+ * model's slice next use 16-byte accesses), head_mode 0, no round_orders on the backward.  A refused request returns non-zero,
+ * leaves a message in nic_last_error and launches nothing. */
+typedef struct NicHorizonEnsemble {
+    int32_t n_models, reserved;
+    int64_t W1, W2, W3, b2, b3;            /* the descriptor's five weight pointers (one packed row per model: five times the same stride) */
+    int64_t z1_obs;                        /* [K][>= H1 * hist_stride] */
+    int64_t rewards, state_final;          /* [K][>= T * ldb], [K][>= F_dyn * ldb] */
+    int64_t state_hist, h1_hist, h2_hist, logits_hist, orders_hist; /* the five histories (ignored where the pointers are NULL) */
+    int64_t dz1, dz2, dz3;                 /* backward: the three pre-activation gradients */
+} NicHorizonEnsemble;
+/* floats of ONE model's slice of every buffer for a descriptor: rows x the row stride the descriptor gives the buffer */
+typedef struct NicHorizonEnsembleSlices {
+    int64_t W1, W2, W3, b2, b3;            /* H1 * ldw1, H2 * ldw2, n_out * ldw3, H2, n_out */
+    int64_t z1_obs;                        /* H1 * hist_stride */
+    int64_t rewards, state_final;          /* T * ldb, F_dyn * ldb */
+    int64_t state_hist, h1_hist, h2_hist, logits_hist, orders_hist; /* F_dyn / H1 / H2 / n_out / S*max(Wn,1) + 2 Wn rows x hist_stride */
+    int64_t dz1, dz2, dz3;                 /* H1 / H2 / n_out rows x hist_stride */
+} NicHorizonEnsembleSlices;
+int nic_horizon_rollout_ensemble_slices(const NicHorizonDesc* d, NicHorizonEnsembleSlices* out);
+/* K forward rollouts (trainer.py:181-216, `simulate_batch`, once per model, under DataDrivenNet.forward, neural_networks.py:430-515)
+ * in one launch; buffers as nic_horizon_rollout_fwd, model 0's.  state_final and the five histories may be NULL. */
+int nic_horizon_rollout_ensemble_fwd(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const float* z1_obs, const float* state0,
+                                     float* rewards, float* state_final, float* state_hist, float* h1_hist, float* h2_hist,
+                                     float* logits_hist, float* orders_hist, void* stream);
+/* K backward sweeps (trainer.py:181-216 under `backward`, once per model; the adjoint of neural_networks.py:430-515) in one launch;
+ * buffers as nic_horizon_rollout_bwd, model 0's.  g_reward is shared. */
+int nic_horizon_rollout_ensemble_bwd(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const float* state_hist, const float* h1_hist,
+                                     const float* h2_hist, const float* logits_hist, const float* orders_hist, NicTable2 g_reward,
+                                     float* dz1_hist, float* dz2_hist, float* dz3_hist, void* stream);
+
 /* ---- fused three-layer 32-wide MLP over gathered inputs (graph policies) -----------------------------------------
  * The GNN policy (neural_networks.py:742-1492) applies five small MLPs (`gnn.yml`: K -> 32 -> 32 -> 32 or 1, ELU inside) to
  * every node / edge of the supply graph of every scenario, on inputs that are concatenations of gathered node / edge

@@ -106,6 +106,20 @@ class NicHorizonDesc(C.Structure):
                    ("hist_stride", C.c_int64), ("head_mode", C.c_int32), ("allow_negative", C.c_int32), ("tape", C.c_void_p)])
 
 
+HORIZON_ENSEMBLE_BUFFERS = ("W1", "W2", "W3", "b2", "b3", "z1_obs", "rewards", "state_final", "state_hist", "h1_hist", "h2_hist",
+                            "logits_hist", "orders_hist", "dz1", "dz2", "dz3")
+
+
+class NicHorizonEnsemble(C.Structure):
+    """K data_driven models in one whole-horizon launch: floats between two models' slices of every per-model buffer
+    (include/nic_rollout.h)"""
+    _fields_ = [("n_models", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_int64) for n in HORIZON_ENSEMBLE_BUFFERS]
+
+
+class NicHorizonEnsembleSlices(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in HORIZON_ENSEMBLE_BUFFERS]
+
+
 class NicClosedFormDesc(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in (
         "n_scenarios", "ldb", "T", "t0", "ignore_periods", "policy", "n_levels", "S", "Ws", "Wn", "Ww", "E", "We",
@@ -235,6 +249,11 @@ PROTOTYPES = {
     "nic_horizon_rollout_ok": (C.c_int, [C.POINTER(NicHorizonDesc)]),
     "nic_horizon_rollout_fwd": (C.c_int, [C.POINTER(NicHorizonDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nic_horizon_rollout_bwd": (C.c_int, [C.POINTER(NicHorizonDesc), _vp, _vp, _vp, _vp, _vp, NicTable2, _vp, _vp, _vp, _vp]),
+    "nic_horizon_rollout_ensemble_slices": (C.c_int, [C.POINTER(NicHorizonDesc), C.POINTER(NicHorizonEnsembleSlices)]),
+    "nic_horizon_rollout_ensemble_fwd": (C.c_int, [C.POINTER(NicHorizonDesc), C.POINTER(NicHorizonEnsemble), _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp, _vp]),
+    "nic_horizon_rollout_ensemble_bwd": (C.c_int, [C.POINTER(NicHorizonDesc), C.POINTER(NicHorizonEnsemble), _vp, _vp, _vp, _vp, _vp,
+                                                   NicTable2, _vp, _vp, _vp, _vp]),
     "nic_gnn_alloc_env_fwd": (C.c_int, [_IOP, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "nic_gnn_alloc_env_bwd": (C.c_int, [_IOP, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, NicTable2, _vp, _vp, _vp, _vp, _vp]),
     "nic_gnn_period_pack_size": (C.c_int, [_i32, _i32]),

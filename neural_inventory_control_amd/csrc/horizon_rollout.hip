@@ -30,6 +30,7 @@
 // Built with -ffp-contract=off (head / env arithmetic rounds like the reference's separate aten ops); the MFMA chains are fma
 // by construction.  Same arithmetic as the per-period route except the summation order inside a layer's contraction.
 #include "env_step_body.h"
+#include "horizon_ensemble_plan.h"
 #include "nic_common.h"
 #include "policy_heads_body.h"
 
@@ -261,6 +262,18 @@ __device__ __forceinline__ f32x4 layer64(const float (&aW)[16], const float* hx,
     return acc + acc1;
 }
 
+// K models in one launch (nic_horizon_rollout_ensemble_*): the kernels' first argument.  Without the flag it IS the descriptor (the
+// same kernel-argument bytes, and `if constexpr` leaves the single-model instantiations the code they were); with it the strides
+// come along, and model m = blockIdx.y advances its weight pointers and its buffers ONCE, at entry, by m x stride as 64-bit pointer
+// arithmetic - every 32-bit element offset below stays an offset inside one model's slice (check_offsets).  Shared by all models:
+// state0, the demand trace, the mask, the tables, g_reward.
+template <bool ENS> struct HzArgs;
+template <> struct HzArgs<false> { NicHorizonDesc d; };
+template <> struct HzArgs<true> { NicHorizonDesc d; NicHorizonEnsemble e; };
+template <class T> __device__ __forceinline__ T* hz_model(T* p, uint32_t model, int64_t stride) {   // (NULL stays NULL: "not passed")
+    return p ? p + nic::horizon_model_offset(model, stride) : p;
+}
+
 // ------------------------------------------------------------------------------------------------------------------------
 // Global memory discipline of both kernels: vmcnt counts loads and stores in issue order, so waiting for ANY prefetched value also
 // drains every store issued before it.  All global traffic of a period is therefore issued in ONE burst at the top of the period
@@ -268,13 +281,31 @@ __device__ __forceinline__ f32x4 layer64(const float (&aW)[16], const float* hx,
 // nothing is waited for until the top of the next period, a whole period of the chain later.
 // (the smallest variant - one-store settings, which the reference trains in batches of 8,192 = 512 workgroups - is held to 256
 // registers so that two workgroups share a CU: one round instead of two)
-template <int MAXW, int MAXS1>
-__global__ __launch_bounds__(kThreads, (MAXS1 == 16 || HZ_FORCE_OCC2) ? 2 : 1) void horizon_fwd_kernel(NicHorizonDesc d, const float* __restrict__ z1_obs,
+template <int MAXW, int MAXS1, bool ENS = false>
+__global__ __launch_bounds__(kThreads, (MAXS1 == 16 || HZ_FORCE_OCC2) ? 2 : 1) void horizon_fwd_kernel(HzArgs<ENS> a, const float* __restrict__ z1_obs,
                                                                 const float* __restrict__ state0, float* __restrict__ rewards,
                                                                 float* __restrict__ state_final, float* __restrict__ state_hist,
                                                                 float* __restrict__ h1_hist, float* __restrict__ h2_hist,
                                                                 float* __restrict__ logits_hist, float* __restrict__ orders_hist) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    NicHorizonDesc d = a.d;
+    if constexpr (ENS) {
+        const uint32_t m = blockIdx.y;
+        const NicHorizonEnsemble& e = a.e;
+        d.W1 = hz_model(d.W1, m, e.W1);
+        d.W2 = hz_model(d.W2, m, e.W2);
+        d.W3 = hz_model(d.W3, m, e.W3);
+        d.b2 = hz_model(d.b2, m, e.b2);
+        d.b3 = hz_model(d.b3, m, e.b3);
+        z1_obs = hz_model(z1_obs, m, e.z1_obs);
+        rewards = hz_model(rewards, m, e.rewards);
+        state_final = hz_model(state_final, m, e.state_final);
+        state_hist = hz_model(state_hist, m, e.state_hist);
+        h1_hist = hz_model(h1_hist, m, e.h1_hist);
+        h2_hist = hz_model(h2_hist, m, e.h2_hist);
+        logits_hist = hz_model(logits_hist, m, e.logits_hist);
+        orders_hist = hz_model(orders_hist, m, e.orders_hist);
+    }
     const NicEnvDims& D = d.io.dims;
     const HzIds I = hz_ids();
     // (32-bit element offsets into every global buffer: the launcher checks that none reaches 2^31)
@@ -529,8 +560,8 @@ __global__ __launch_bounds__(kThreads, (MAXS1 == 16 || HZ_FORCE_OCC2) ? 2 : 1) v
 // the data_driven head's adjoint (per-warehouse reductions in store order between two barriers), then the three input-gradient
 // contractions on resident TRANSPOSED weight fragments - the first layer's only over the state rows (nothing else of the input
 // carries a gradient back in time).
-template <int MAXW, int VAR>
-__global__ __launch_bounds__(kThreads, (VAR == 0 || HZ_FORCE_OCC2) ? 2 : 1) void horizon_bwd_kernel(NicHorizonDesc d, const float* __restrict__ state_hist,
+template <int MAXW, int VAR, bool ENS = false>
+__global__ __launch_bounds__(kThreads, (VAR == 0 || HZ_FORCE_OCC2) ? 2 : 1) void horizon_bwd_kernel(HzArgs<ENS> a, const float* __restrict__ state_hist,
                                                                 const float* __restrict__ h1_hist, const float* __restrict__ h2_hist,
                                                                 const float* __restrict__ logits_hist,
                                                                 const float* __restrict__ orders_hist, NicTable2 g_reward,
@@ -538,6 +569,22 @@ __global__ __launch_bounds__(kThreads, (VAR == 0 || HZ_FORCE_OCC2) ? 2 : 1) void
                                                                 float* __restrict__ dz3_hist) {
     constexpr int MAXT1 = VAR == 0 ? 1 : (VAR == 1 ? 3 : 4), MAXS3 = VAR == 0 ? 4 : (VAR == 1 ? 20 : 32);
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    NicHorizonDesc d = a.d;
+    if constexpr (ENS) {
+        const uint32_t m = blockIdx.y;
+        const NicHorizonEnsemble& e = a.e;
+        d.W1 = hz_model(d.W1, m, e.W1);
+        d.W2 = hz_model(d.W2, m, e.W2);
+        d.W3 = hz_model(d.W3, m, e.W3);
+        state_hist = hz_model(state_hist, m, e.state_hist);
+        h1_hist = hz_model(h1_hist, m, e.h1_hist);
+        h2_hist = hz_model(h2_hist, m, e.h2_hist);
+        logits_hist = hz_model(logits_hist, m, e.logits_hist);
+        orders_hist = hz_model(orders_hist, m, e.orders_hist);
+        dz1_hist = hz_model(dz1_hist, m, e.dz1);
+        dz2_hist = hz_model(dz2_hist, m, e.dz2);
+        dz3_hist = hz_model(dz3_hist, m, e.dz3);
+    }
     const NicEnvDims& D = d.io.dims;
     const HzIds I = hz_ids();
     // (32-bit element offsets into every global buffer: the launcher checks that none reaches 2^31)
@@ -804,6 +851,89 @@ int allow_lds(K kernel, int bytes, const char* who) {
     return 0;
 }
 
+// The two launchers.  e == nullptr: the single-model kernels (grid y = 1, the descriptor alone); else the ensemble instantiations, one
+// grid row per model, after csrc/horizon_ensemble_plan.h's checks - a refused request launches nothing.
+int launch_fwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsemble* e, const float* z1_obs, const float* state0,
+               float* rewards, float* state_final, float* state_hist, float* h1_hist, float* h2_hist, float* logits_hist,
+               float* orders_hist, void* stream) {
+    if (int r = validate(d, who)) return r;
+    if (int r = check_offsets(d, who)) return r;
+    NIC_REQUIRE((z1_obs || d->head_mode != 0) && state0 && rewards, "%s: null z1_obs / state0 / rewards", who);
+    NIC_REQUIRE(!state_hist || (orders_hist && (d->head_mode != 0 || (h1_hist && h2_hist && logits_hist))), "%s: histories come together",
+                who);
+    if (e) {
+        const int why = nic::horizon_ensemble_check_fwd(*d, *e, nic::horizon_ensemble_slices(*d), state_final != nullptr, state_hist != nullptr);
+        NIC_REQUIRE(why == 0, "%s: %s (%d models)", who, nic::horizon_ensemble_reason(why), e->n_models);
+    }
+    const NicEnvDims& D = d->io.dims;
+    const int FD = D.n_stores * D.store_slots + D.n_warehouses * D.warehouse_slots;
+    const int bytes = lds_bytes(d, false);
+    NIC_REQUIRE(bytes <= 160 * 1024, "%s: %d bytes of LDS", who, bytes);
+    const dim3 grid(nic::ceil_div(D.n_scenarios, NB), e ? e->n_models : 1), block(kThreads);
+    hipStream_t s = nic::as_stream(stream);
+    const int steps = fwd_steps(FD);
+    if (e) nic::note_kernelf("horizon_fwd_kernel<8,%d,models=%d>", steps, e->n_models);
+    else nic::note_kernelf("horizon_fwd_kernel<8,%d>", steps);
+#define NIC_HZ_FWD(S1)                                                                                                          \
+    do {                                                                                                                        \
+        if (e) {                                                                                                                \
+            if (int r = allow_lds(horizon_fwd_kernel<8, S1, true>, bytes, who)) return r;                                       \
+            hipLaunchKernelGGL((horizon_fwd_kernel<8, S1, true>), grid, block, bytes, s, HzArgs<true>{*d, *e}, z1_obs, state0,   \
+                               rewards, state_final, state_hist, h1_hist, h2_hist, logits_hist, orders_hist);                   \
+        } else {                                                                                                                \
+            if (int r = allow_lds(horizon_fwd_kernel<8, S1>, bytes, who)) return r;                                             \
+            hipLaunchKernelGGL((horizon_fwd_kernel<8, S1>), grid, block, bytes, s, HzArgs<false>{*d}, z1_obs, state0, rewards,   \
+                               state_final, state_hist, h1_hist, h2_hist, logits_hist, orders_hist);                            \
+        }                                                                                                                       \
+    } while (0)
+    if (steps == 16) NIC_HZ_FWD(16);
+    else if (steps == 40) NIC_HZ_FWD(40);
+    else NIC_HZ_FWD(64);
+#undef NIC_HZ_FWD
+    return nic::check_launch(who);
+}
+
+int launch_bwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsemble* e, const float* state_hist, const float* h1_hist,
+               const float* h2_hist, const float* logits_hist, const float* orders_hist, NicTable2 g_reward, float* dz1_hist,
+               float* dz2_hist, float* dz3_hist, void* stream) {
+    if (int r = validate(d, who)) return r;
+    if (int r = check_offsets(d, who)) return r;
+    NIC_REQUIRE(d->head_mode != 1, "%s: an order tape has no gradient", who);
+    NIC_REQUIRE(state_hist && orders_hist && g_reward.p && dz3_hist, "%s: null buffer", who);
+    NIC_REQUIRE(d->head_mode != 0 || (h1_hist && h2_hist && logits_hist && dz1_hist && dz2_hist), "%s: null buffer", who);
+    NIC_REQUIRE(!d->round_orders, "%s: rounded orders have no gradient (evaluation only)", who);
+    if (e) {
+        const int why = nic::horizon_ensemble_check_bwd(*d, *e, nic::horizon_ensemble_slices(*d));
+        NIC_REQUIRE(why == 0, "%s: %s (%d models)", who, nic::horizon_ensemble_reason(why), e->n_models);
+    }
+    const NicEnvDims& D = d->io.dims;
+    const int FD = D.n_stores * D.store_slots + D.n_warehouses * D.warehouse_slots;
+    const int bytes = lds_bytes(d, true);
+    NIC_REQUIRE(bytes <= 160 * 1024, "%s: %d bytes of LDS", who, bytes);
+    const dim3 grid(nic::ceil_div(D.n_scenarios, NB), e ? e->n_models : 1), block(kThreads);
+    hipStream_t s = nic::as_stream(stream);
+    const int var = bwd_variant(FD, d->n_out);
+    if (e) nic::note_kernelf("horizon_bwd_kernel<8,%d,models=%d>", var, e->n_models);
+    else nic::note_kernelf("horizon_bwd_kernel<8,%d>", var);
+#define NIC_HZ_BWD(V)                                                                                                           \
+    do {                                                                                                                        \
+        if (e) {                                                                                                                \
+            if (int r = allow_lds(horizon_bwd_kernel<8, V, true>, bytes, who)) return r;                                        \
+            hipLaunchKernelGGL((horizon_bwd_kernel<8, V, true>), grid, block, bytes, s, HzArgs<true>{*d, *e}, state_hist, h1_hist, \
+                               h2_hist, logits_hist, orders_hist, g_reward, dz1_hist, dz2_hist, dz3_hist);                      \
+        } else {                                                                                                                \
+            if (int r = allow_lds(horizon_bwd_kernel<8, V>, bytes, who)) return r;                                              \
+            hipLaunchKernelGGL((horizon_bwd_kernel<8, V>), grid, block, bytes, s, HzArgs<false>{*d}, state_hist, h1_hist,        \
+                               h2_hist, logits_hist, orders_hist, g_reward, dz1_hist, dz2_hist, dz3_hist);                      \
+        }                                                                                                                       \
+    } while (0)
+    if (var == 0) NIC_HZ_BWD(0);
+    else if (var == 1) NIC_HZ_BWD(1);
+    else NIC_HZ_BWD(2);
+#undef NIC_HZ_BWD
+    return nic::check_launch(who);
+}
+
 }  // namespace
 
 #ifdef NIC_TUNING_BUILD
@@ -823,59 +953,38 @@ int nic_horizon_rollout_ok(const NicHorizonDesc* d) {
 int nic_horizon_rollout_fwd(const NicHorizonDesc* d, const float* z1_obs, const float* state0, float* rewards, float* state_final,
                             float* state_hist, float* h1_hist, float* h2_hist, float* logits_hist, float* orders_hist,
                             void* stream) {
-    if (int e = validate(d, "nic_horizon_rollout_fwd")) return e;
-    if (int e = check_offsets(d, "nic_horizon_rollout_fwd")) return e;
-    NIC_REQUIRE((z1_obs || d->head_mode != 0) && state0 && rewards, "nic_horizon_rollout_fwd: null z1_obs / state0 / rewards");
-    NIC_REQUIRE(!state_hist || (orders_hist && (d->head_mode != 0 || (h1_hist && h2_hist && logits_hist))),
-                "nic_horizon_rollout_fwd: histories come together");
-    const NicEnvDims& D = d->io.dims;
-    const int FD = D.n_stores * D.store_slots + D.n_warehouses * D.warehouse_slots;
-    const int bytes = lds_bytes(d, false);
-    NIC_REQUIRE(bytes <= 160 * 1024, "nic_horizon_rollout_fwd: %d bytes of LDS", bytes);
-    const dim3 grid(nic::ceil_div(D.n_scenarios, NB)), block(kThreads);
-    hipStream_t s = nic::as_stream(stream);
-    const int steps = fwd_steps(FD);
-    nic::note_kernelf("horizon_fwd_kernel<8,%d>", steps);
-#define NIC_HZ_FWD(S1)                                                                                                      \
-    do {                                                                                                                    \
-        if (int e = allow_lds(horizon_fwd_kernel<8, S1>, bytes, "nic_horizon_rollout_fwd")) return e;                        \
-        hipLaunchKernelGGL((horizon_fwd_kernel<8, S1>), grid, block, bytes, s, *d, z1_obs, state0, rewards, state_final,     \
-                           state_hist, h1_hist, h2_hist, logits_hist, orders_hist);                                         \
-    } while (0)
-    if (steps == 16) NIC_HZ_FWD(16);
-    else if (steps == 40) NIC_HZ_FWD(40);
-    else NIC_HZ_FWD(64);
-#undef NIC_HZ_FWD
-    return nic::check_launch("nic_horizon_rollout_fwd");
+    return launch_fwd("nic_horizon_rollout_fwd", d, nullptr, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist,
+                      logits_hist, orders_hist, stream);
 }
 
 int nic_horizon_rollout_bwd(const NicHorizonDesc* d, const float* state_hist, const float* h1_hist, const float* h2_hist,
                             const float* logits_hist, const float* orders_hist, NicTable2 g_reward, float* dz1_hist,
                             float* dz2_hist, float* dz3_hist, void* stream) {
-    if (int e = validate(d, "nic_horizon_rollout_bwd")) return e;
-    if (int e = check_offsets(d, "nic_horizon_rollout_bwd")) return e;
-    NIC_REQUIRE(d->head_mode != 1, "nic_horizon_rollout_bwd: an order tape has no gradient");
-    NIC_REQUIRE(state_hist && orders_hist && g_reward.p && dz3_hist, "nic_horizon_rollout_bwd: null buffer");
-    NIC_REQUIRE(d->head_mode != 0 || (h1_hist && h2_hist && logits_hist && dz1_hist && dz2_hist), "nic_horizon_rollout_bwd: null buffer");
-    NIC_REQUIRE(!d->round_orders, "nic_horizon_rollout_bwd: rounded orders have no gradient (evaluation only)");
-    const NicEnvDims& D = d->io.dims;
-    const int FD = D.n_stores * D.store_slots + D.n_warehouses * D.warehouse_slots;
-    const int bytes = lds_bytes(d, true);
-    NIC_REQUIRE(bytes <= 160 * 1024, "nic_horizon_rollout_bwd: %d bytes of LDS", bytes);
-    const dim3 grid(nic::ceil_div(D.n_scenarios, NB)), block(kThreads);
-    hipStream_t s = nic::as_stream(stream);
-    const int var = bwd_variant(FD, d->n_out);
-    nic::note_kernelf("horizon_bwd_kernel<8,%d>", var);
-#define NIC_HZ_BWD(V)                                                                                                       \
-    do {                                                                                                                    \
-        if (int e = allow_lds(horizon_bwd_kernel<8, V>, bytes, "nic_horizon_rollout_bwd")) return e;                         \
-        hipLaunchKernelGGL((horizon_bwd_kernel<8, V>), grid, block, bytes, s, *d, state_hist, h1_hist, h2_hist, logits_hist, \
-                           orders_hist, g_reward, dz1_hist, dz2_hist, dz3_hist);                                            \
-    } while (0)
-    if (var == 0) NIC_HZ_BWD(0);
-    else if (var == 1) NIC_HZ_BWD(1);
-    else NIC_HZ_BWD(2);
-#undef NIC_HZ_BWD
-    return nic::check_launch("nic_horizon_rollout_bwd");
+    return launch_bwd("nic_horizon_rollout_bwd", d, nullptr, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward, dz1_hist,
+                      dz2_hist, dz3_hist, stream);
+}
+
+int nic_horizon_rollout_ensemble_slices(const NicHorizonDesc* d, NicHorizonEnsembleSlices* out) {
+    NIC_REQUIRE(out != nullptr, "nic_horizon_rollout_ensemble_slices: null output");
+    if (int e = validate(d, "nic_horizon_rollout_ensemble_slices")) return e;
+    NIC_REQUIRE(d->head_mode == 0, "nic_horizon_rollout_ensemble_slices: %s", nic::horizon_ensemble_reason(nic::HE_HEAD_MODE));
+    *out = nic::horizon_ensemble_slices(*d);
+    return 0;
+}
+
+int nic_horizon_rollout_ensemble_fwd(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const float* z1_obs, const float* state0,
+                                     float* rewards, float* state_final, float* state_hist, float* h1_hist, float* h2_hist,
+                                     float* logits_hist, float* orders_hist, void* stream) {
+    NIC_REQUIRE(e != nullptr, "nic_horizon_rollout_ensemble_fwd: null ensemble");
+    return launch_fwd("nic_horizon_rollout_ensemble_fwd", d, e, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist,
+                      logits_hist, orders_hist, stream);
+}
+
+int nic_horizon_rollout_ensemble_bwd(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const float* state_hist, const float* h1_hist,
+                                     const float* h2_hist, const float* logits_hist, const float* orders_hist, NicTable2 g_reward,
+                                     float* dz1_hist, float* dz2_hist, float* dz3_hist, void* stream) {
+    NIC_REQUIRE(e != nullptr, "nic_horizon_rollout_ensemble_bwd: null ensemble");
+    return launch_bwd("nic_horizon_rollout_ensemble_bwd", d, e, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward, dz1_hist,
+                      dz2_hist, dz3_hist, stream);
 }
 }

@@ -1,0 +1,276 @@
+"""`HorizonPolicyEnsemble`: K `data_driven` policies of ONE architecture (DataDrivenNet, neural_networks.py:430-515) trained or
+evaluated on ONE real-data batch with one forward and one backward whole-horizon launch for all of them
+(`nic_horizon_rollout_ensemble_*`, csrc/horizon_rollout.hip: grid y = model).
+
+A whole-horizon launch of the reference's real-data batch (72 products x 21 stores x 3 warehouses x 95 weeks) has ceil(72 / 16) = 5
+workgroups: a serial chain of 95 periods on 2 % of the device.  Seeds, learning rates or initialisations of one architecture ride in
+the idle CUs instead of paying K steps.  Every model runs the instruction stream of the single-model kernels on its own slice of
+the buffers, and the four GEMMs around the launch pair (the observation rows' share of the first layer, three weight gradients)
+are launched per model with the operands, shapes and strides `FusedRollout`'s whole-horizon route uses - so each model's costs,
+final state and gradients are the bits `FusedRollout(model).run` gives for it (trainer.py:181-216 once per model).  The totals are
+one fixed-order reduction for all K models (the cost half of `nic_small_rollout_ensemble_reduce`): they agree with the single-model
+`torch.sum` to rounding, not to the bit.
+
+Layout: weights `[K][P]` in `nn.Linear`'s own order (per layer the weight, row-major, then the bias; packed with one `torch.cat`
+per run - an `EnsembleAdam(K, P)` can step such a buffer), gradients `[K][P]` in the same order (`param.grad` are views of it),
+inputs `X [K][F][T][ldb]` (the kernel writes model m's state rows into X[m]; the observation rows are model-independent, filled once
+and copied), `z1_obs [K][H1][T][ldb]`, costs `rewards [K][T][ldb]`, histories and pre-activation gradients `[K][rows][T][ldb]`.
+
+Not part of this engine: `bind_parameters` / `train_step` / `fit`, graph replay, problem instances per model, Trainer / YAML /
+`main_run` wiring, a `torch.library` operator, multi-GPU sharding.  The optimizer is the caller's (K optimizers, or one with K
+parameter groups, step the models independently).
+"""
+import types
+
+import torch
+
+from . import _lib, ops
+from . import horizon_rollout as hz
+from . import small_rollout as sr
+from .layout import demand_trace_soa, Table
+from .rollout import _pad32, FusedRollout
+from .small_ensemble import pack_ensemble_weights
+
+MAX_MODELS = 65535
+
+
+def _layer_sizes(model):
+    a = model.nn_args
+    return tuple(a["neurons_per_hidden_layer"]["master"]) + (a["output_sizes"]["master"],)
+
+
+def check_models(models):
+    """The models an ensemble takes: 1 <= K <= 65535 `data_driven` policies `FusedRollout` takes, with the same layer sizes (two
+    hidden layers: what the whole-horizon kernels run) and a bias in every layer.  ValueError names the first mismatch.  Host-side
+    only; the setting's side of `HorizonPlan.supports` is checked when the first batch arrives."""
+    models = list(models)
+    if len(models) < 1:
+        raise ValueError("HorizonPolicyEnsemble needs at least one model")
+    if len(models) > MAX_MODELS:
+        raise ValueError("HorizonPolicyEnsemble takes at most 65,535 models")
+    for i, m in enumerate(models):
+        name = getattr(m, "nn_args", {}).get("name") if hasattr(m, "nn_args") else None
+        if name != "data_driven" or not FusedRollout.supports(m):
+            raise ValueError(f"model {i}: HorizonPolicyEnsemble handles the data_driven policy (ELU inside, ReLU on the output), got {name!r}")
+        if _layer_sizes(m) != _layer_sizes(models[0]):
+            raise ValueError(f"model {i}: layer sizes {list(_layer_sizes(m))} differ from model 0's {list(_layer_sizes(models[0]))}")
+        if any(lin.bias is None for lin in m.master_linears()):
+            raise ValueError(f"model {i}: a layer without bias")
+    return models
+
+
+def layer_slices(dims):
+    """[(weight offset, rows, cols, bias offset)] per layer of one model's packed row; dims = [F, H1, ..., n_out]"""
+    out, off = [], 0
+    for k, n in zip(dims[:-1], dims[1:]):
+        out.append((off, n, k, off + n * k))
+        off += n * k + n
+    return out
+
+
+def packed_count(dims):
+    return sum(n * k + n for k, n in zip(dims[:-1], dims[1:]))
+
+
+def grad_views(grad, dims):
+    """[(weight gradients per layer, bias gradients per layer)] per model: views into grad [K][>= P] in the packed-weight layout"""
+    sl = layer_slices(dims)
+    return [([grad[m, o:o + n * k].view(n, k) for o, n, k, _ in sl], [grad[m, bo:bo + n] for _, n, _, bo in sl])
+            for m in range(grad.shape[0])]
+
+
+class HorizonPolicyEnsemble:
+    def __init__(self, models, problem_params, device):
+        self.models = check_models(models)
+        _lib.require_device()
+        self.problem_params = problem_params
+        self.device = torch.device(device)
+        # (one single-model engine per model: problem cache, LazyLinear materialisation and the observation rows are theirs; they
+        # allocate nothing until they run, and they never run here)
+        self._engines = [FusedRollout(m, problem_params, device) for m in self.models]
+        self.last_kernels = {}   # launch class -> kernel name the library recorded in the last run
+        self._key = None
+        self.plan = self.prob = None
+        self.weights = self.grad = self._grad_views = None   # [K][P], [K][P]
+
+    @property
+    def n_models(self):
+        return len(self.models)
+
+    def _dims(self, F):
+        for eng in self._engines:
+            eng.materialize(F)
+        lins = [eng._linears() for eng in self._engines]
+        dims = [[ls[0].in_features] + [m.out_features for m in ls] for ls in lins]
+        for i, d in enumerate(dims):
+            if d != dims[0]:
+                raise ValueError(f"model {i}: layer sizes {d} differ from model 0's {dims[0]}")
+        return lins, dims[0]
+
+    def _setup(self, prob, T, train, dims, shift):
+        K, dev, ld = self.n_models, self.device, prob.ldb
+        key = (prob.B, T, K, tuple(dims), prob.S, prob.Wn, prob.Ws, prob.Ww, shift)
+        if self._key != key:
+            self._key = None
+            for name in ("X", "z1", "W1obs", "hist", "dz", "slabs", "rewards", "final", "state0", "scratch", "totals"):
+                setattr(self, name, None)   # release the previous shape's buffers before sizing the new ones
+            F, FD = dims[0], prob.S * prob.Ws + prob.Wn * prob.Ww
+            if not hz.HorizonPlan.supports(prob, "data_driven", dims) or not hz.offsets_ok(prob, T, T + shift, hz.MAX_HIDDEN):
+                raise ValueError(f"HorizonPolicyEnsemble: the whole-horizon kernels do not take this setting / policy (layer sizes {dims}, "
+                                 f"{FD} state rows, {prob.B} scenarios x {T} periods)")
+            self.plan = hz.HorizonPlan(prob, dims)
+            z = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
+            P = packed_count(dims)
+            if self.weights is None or self.weights.shape[1] != P:
+                self.weights, self.grad, self._grad_views = z(K, P), None, None
+            self.F, self.F_dyn, self.dims = F, FD, list(dims)
+            self.state0 = z(FD, ld)
+            self.rewards, self.final = z(K, T, ld), z(K, FD, ld)
+            self.X = z(K, F, T, ld)       # rows [0, FD): state before period t (written by the kernel); then the observation rows
+            self.z1 = z(K, dims[1], T, ld)
+            self.W1obs = z(K, dims[1], _pad32(F - FD))   # (rows padded to 32 floats, as FusedRollout's: the GEMM's A-tile loads are float4)
+            if prob.Wn:
+                conn = self.problem_params["warehouse_store_adjacency"]
+                self.edge_mask = torch.tensor(conn, dtype=torch.float32, device=dev).t().contiguous()   # [S][Wn]
+            else:
+                self.edge_mask = None
+            self.totals = z(K, 2)
+            n_scratch = sr.small_rollout_reduce_scratch(0, 0, T * ld)
+            self.scratch = torch.empty(K, n_scratch, device=dev)
+            self._reduce = sr.ensemble_strides(K, rewards=T * ld, scratch=n_scratch)
+            self._strides = None
+            self._checked = False
+            self._key = key
+        if train and self.hist is None:
+            # the training buffers come with the first training run of a shape and stay: evaluation runs in between use the rest
+            z = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
+            n_cols = T * ld
+            rows = [dims[1], dims[2], dims[3], self.plan.n_ord + prob.Wn]   # h1, h2, logits, orders (+ shipped)
+            self.hist = [z(K, r, T, ld) for r in rows]
+            self.dz = [z(K, dims[i + 1], T, ld) for i in range(3)]   # (padding columns stay zero: the kernel writes live ones only)
+            self.g_reward, self._g_reward_key = z(ld), None
+            # (one set of slabs: the K weight-gradient contractions of a layer follow each other on the stream)
+            self.splits = [ops.wgrad_num_splits(dims[i + 1], dims[i], n_cols) for i in range(3)]
+            self.slabs = [z(self.splits[i], dims[i + 1], (dims[i] + 1 + 3) // 4 * 4) for i in range(3)]
+            if self.grad is None:
+                self.grad = z(K, self.weights.shape[1])
+                self._grad_views = grad_views(self.grad, dims)
+            self._strides = None
+
+    def _ensemble(self, desc, train):
+        """NicHorizonEnsemble of the current buffers, checked once per shape against csrc/horizon_ensemble_plan.h's slices"""
+        if self._strides is None or self._strides[0] != bool(train):
+            P = self.weights.shape[1]
+            st = dict(W1=P, W2=P, W3=P, b2=P, b3=P, z1_obs=self.z1[0].numel(), rewards=self.rewards[0].numel(),
+                      state_final=self.final[0].numel())
+            if train:
+                st.update(state_hist=self.X[0].numel(), h1_hist=self.hist[0][0].numel(), h2_hist=self.hist[1][0].numel(),
+                          logits_hist=self.hist[2][0].numel(), orders_hist=self.hist[3][0].numel(), dz1=self.dz[0][0].numel(),
+                          dz2=self.dz[1][0].numel(), dz3=self.dz[2][0].numel())
+            sl = hz.ensemble_slices(desc)
+            assert all(v >= sl[k] for k, v in st.items()), (st, sl)
+            self._strides = (bool(train), hz.ensemble_strides(self.n_models, **st))
+        return self._strides[1]
+
+    def param_grads(self):
+        """[(parameter, gradient view into the [K][P] buffer of the last training run)] over all models"""
+        out = []
+        for eng, (gw, gb) in zip(self._engines, self._grad_views):
+            for i, m in enumerate(eng._linears()):
+                out += [(m.weight, gw[i]), (m.bias, gb[i])]
+        return out
+
+    def _note(self, tag):
+        name = _lib.lib().nic_last_kernel()
+        self.last_kernels[tag] = name.decode() if name else None
+
+    # ---- one batch ---------------------------------------------------------------------------------------------------------------
+    def run(self, data, periods, ignore_periods=0, train=True, observation_params=None, grad_scale=None, accumulate_grads=False,
+            discrete_allocation=False):
+        """Rollout of one batch under every model (and, if `train`, d(mean loss)/d(theta) into every model's `param.grad`: views
+        into one [K][P] gradient buffer, `accumulate_grads` adds - `small_rollout.assign_grads`).  Arguments as `FusedRollout.run`.
+        Returns (total [K], reported [K]) device tensors; `rewards` [K][T][ldb] holds the per-period costs.  A setting the
+        whole-horizon kernels do not take is a ValueError: there is no fall-back to K single steps."""
+        if discrete_allocation and train:
+            raise ValueError("discrete_allocation is an evaluation-time option of the fused rollout")
+        lead, dev, K = self._engines[0], self.device, self.n_models
+        if not FusedRollout.observation_ok(self.models[0], observation_params, data):
+            raise ValueError("data_driven needs a past-demand window and the days_from_christmas time feature")
+        prob = self.prob = lead._problem_for(data)
+        T, B, ld = periods, prob.B, prob.ldb
+        shift = observation_params["demand"]["period_shift"]
+        P_ = observation_params["demand"]["past_periods"]
+        FD = prob.S * prob.Ws + prob.Wn * prob.Ww
+        F = FD + prob.S * P_ + 2 * prob.S + data["days_from_christmas"].shape[1] + prob.S * data["lead_times"].shape[2]
+        lins, dims = self._dims(F)
+        if prob.E != 0 or len(dims) != 4:
+            raise ValueError(f"HorizonPolicyEnsemble: the whole-horizon kernels do not take this setting / policy (layer sizes {dims}, "
+                             f"{prob.E} extra echelons)")
+        demand_soa = demand_trace_soa(data["demands"], ld, dev)
+        if demand_soa.shape[0] < T + shift:
+            raise ValueError("Current period is greater than the number of periods in the data")
+        self._setup(prob, T, train, dims, shift)
+        Fo, n_cols = F - FD, T * ld
+        pack_ensemble_weights(lins, self.weights)   # (every run: the optimizers moved the parameters)
+        a = prob.S * prob.Ws
+        self.state0[:a].view(prob.S, prob.Ws, ld)[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
+        if prob.Wn:
+            self.state0[a:].view(prob.Wn, prob.Ww, ld)[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
+        # the observation rows are the same for every model: filled once (FusedRollout's own routine), copied to the other K - 1
+        X = self.X
+        lead.F, lead.F_dyn = F, FD   # (what the routine reads of its engine besides the window scratch it keeps: the row counts)
+        lead._fill_observation_rows(X[0].transpose(0, 1), data, prob, T, shift, observation_params, demand_soa)
+        if K > 1:
+            X[1:, FD:].copy_(X[0, FD:].unsqueeze(0).expand(K - 1, Fo, T, ld))
+        # per model, with the single-model route's operands: the observation rows' share of the first layer for every period (+ bias)
+        for m, ls in enumerate(lins):
+            self.W1obs[m, :, :Fo].copy_(ls[0].weight.detach()[:, FD:])
+            ops.linear_fwd(self.W1obs[m, :, :Fo], ls[0].bias.detach(), X[m, FD:].view(Fo, n_cols), self.z1[m].view(dims[1], n_cols), n_cols,
+                           _lib.NIC_ACT_NONE)
+        # the descriptor points at model 0's row of the packed weights
+        row0 = self.weights[0]
+        views = [types.SimpleNamespace(weight=row0[o:o + n * k].view(n, k), bias=row0[bo:bo + n]) for o, n, k, bo in layer_slices(dims)]
+        desc = self.plan.desc(prob, T, shift, views, self.edge_mask, demand_soa, n_cols, round_orders=discrete_allocation)
+        if not self._checked:   # once per shape: the library's own limits
+            if not hz.horizon_ok(desc):
+                msg = _lib.lib().nic_last_error()
+                raise ValueError("HorizonPolicyEnsemble: the whole-horizon kernels do not take this shape: " + (msg.decode() if msg else "?"))
+            self._checked = True
+        ens = self._ensemble(desc, train)
+        hist = ([X] + self.hist) if train else [None] * 5
+        hz.horizon_ensemble_fwd(desc, ens, self.z1, self.state0, self.rewards, self.final, *hist)
+        self._note("fwd")
+        # every model's total / reported cost: one fixed-order reduction (two launches) for all K
+        sr.small_rollout_ensemble_reduce(self._reduce, None, 0, 0, 0, None, self.rewards, n_cols, ignore_periods * ld, self.totals,
+                                         self.scratch)
+        tt = self.totals.clone()   # (the caller's tensors must not change under a later run)
+        if not train:
+            return tt[:, 0], tt[:, 1]
+        if grad_scale is None:
+            grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
+        self._g_reward_key = sr.set_g_reward(self.g_reward, B, grad_scale, self._g_reward_key)
+        hz.horizon_ensemble_bwd(desc, ens, *hist, Table(self.g_reward, 0, 1), *self.dz)
+        self._note("bwd")
+        # three weight gradients per model: FusedRollout._wgrad_over_columns' launches on model m's slices
+        for m, (gw, gb) in enumerate(self._grad_views):
+            inputs = [X[m], self.hist[0][m], self.hist[1][m]]
+            for i, x in enumerate(inputs):
+                self.slabs[i].zero_()
+                ops.linear_wgrad(self.dz[i][m].flatten(1), x.flatten(1), self.slabs[i], n_cols)
+                ops.wgrad_reduce(self.slabs[i], gw[i], gb[i], dims[i], 1.0)
+        sr.assign_grads(self.param_grads(), accumulate_grads)
+        return tt[:, 0], tt[:, 1]
+
+    # ---- inspection helpers used by the parity tests --------------------------------------------------------------------------------
+    def per_period_rewards(self):
+        """[K][T][B]"""
+        return self.rewards[:, :, :self.prob.B]
+
+    def final_state(self, m):
+        """model m's state after the last period, as `FusedRollout.final_state`"""
+        from .layout import ref_view
+        prob, a = self.prob, self.prob.S * self.prob.Ws
+        out = {"store_inventories": ref_view(self.final[m, :a].view(prob.S, prob.Ws, -1), prob.B)}
+        if prob.Wn:
+            out["warehouse_inventories"] = ref_view(self.final[m, a:].view(prob.Wn, prob.Ww, -1), prob.B)
+        return out

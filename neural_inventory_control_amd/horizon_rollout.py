@@ -73,3 +73,43 @@ def horizon_bwd(desc, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_
     p = _lib.ptr
     _lib.check(_lib.lib().nic_horizon_rollout_bwd(desc, p(state_hist), p(h1_hist), p(h2_hist), p(logits_hist), p(orders_hist),
                                                   g_reward.t2(), p(dz1), p(dz2), p(dz3), _lib.current_stream()))
+
+
+# ---- K models of one architecture on one batch (nic_horizon_rollout_ensemble_*, csrc/horizon_ensemble_plan.h) -----------------------
+ENSEMBLE_BUFFERS = _lib.HORIZON_ENSEMBLE_BUFFERS
+
+
+def ensemble_slices(desc):
+    """{buffer: floats of ONE model's slice} for a descriptor - the numbers the entry points check the strides against, from
+    csrc/horizon_ensemble_plan.h.  Needs the library, not a device."""
+    out = _lib.NicHorizonEnsembleSlices()
+    _lib.check(_lib.lib().nic_horizon_rollout_ensemble_slices(desc, out))
+    return {n: int(getattr(out, n)) for n in ENSEMBLE_BUFFERS}
+
+
+def ensemble_strides(n_models, **strides):
+    """NicHorizonEnsemble: floats between two models' slices of every per-model buffer (buffers a call does not take: 0)."""
+    e = _lib.NicHorizonEnsemble()
+    e.n_models = int(n_models)
+    for k, v in strides.items():
+        if k not in ENSEMBLE_BUFFERS:
+            raise KeyError(k)
+        setattr(e, k, int(v))
+    return e
+
+
+def horizon_ensemble_fwd(desc, ens, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist, logits_hist, orders_hist):
+    """`horizon_fwd` for ens.n_models models in one launch: `desc` and every buffer are model 0's, model m's start m x its stride behind."""
+    ops._dev(rewards)
+    p = _lib.ptr
+    _lib.check(_lib.lib().nic_horizon_rollout_ensemble_fwd(desc, ens, p(z1_obs), p(state0), p(rewards), p(state_final), p(state_hist),
+                                                           p(h1_hist), p(h2_hist), p(logits_hist), p(orders_hist),
+                                                           _lib.current_stream()))
+
+
+def horizon_ensemble_bwd(desc, ens, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward: Table, dz1, dz2, dz3):
+    ops._dev(dz1)
+    p = _lib.ptr
+    _lib.check(_lib.lib().nic_horizon_rollout_ensemble_bwd(desc, ens, p(state_hist), p(h1_hist), p(h2_hist), p(logits_hist),
+                                                           p(orders_hist), g_reward.t2(), p(dz1), p(dz2), p(dz3),
+                                                           _lib.current_stream()))

@@ -1,0 +1,325 @@
+"""Host side of the K-models-in-one-launch route for the data_driven policy (nic_horizon_rollout_ensemble_*): the slice sizes and the
+validator of csrc/horizon_ensemble_plan.h through a stand-alone program built with the host compiler, the C declarations against
+their ctypes prototypes, the [K][P] weight packing, the gradient views and the refusals that need no device."""
+import copy
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+import torch
+
+from golden_io import Golden
+from neural_inventory_control_amd import _lib, build, horizon_ensemble as he, horizon_rollout as hz, small_rollout as sr
+from neural_inventory_control_amd.neural_networks import NeuralNetworkCreator
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BUFFERS = ("W1", "W2", "W3", "b2", "b3", "z1_obs", "rewards", "state_final", "state_hist", "h1_hist", "h2_hist", "logits_hist",
+           "orders_hist", "dz1", "dz2", "dz3")
+HISTORIES = ("state_hist", "h1_hist", "h2_hist", "logits_hist", "orders_hist")
+ALIGNED = ("z1_obs", "rewards", "state_final") + HISTORIES + ("dz1", "dz2", "dz3")
+# (S, Wn, Ws, Ww, ldb, T, H1, H2, F): the reference's real-data batch (72 products -> ldb 128, 597 input rows), the many-warehouse
+# fixture's horizon, the one-store real-data batch, a stores-only setting with odd widths
+SHAPES = [(21, 3, 6, 3, 128, 95, 64, 64, 597), (21, 3, 6, 3, 64, 10, 64, 64, 597), (1, 0, 8, 0, 8192, 95, 64, 64, 30),
+          (5, 0, 3, 0, 64, 7, 17, 33, 41)]
+
+
+def _host_clang():
+    hipcc = os.path.realpath(shutil.which(build._hipcc()) or build._hipcc())
+    for c in (os.path.join(os.path.dirname(hipcc), "..", "llvm", "bin", "clang++"), "/opt/rocm/llvm/bin/clang++",
+              shutil.which("clang++"), shutil.which("g++")):
+        if c and os.path.isfile(c):
+            return c
+    raise RuntimeError("no host C++ compiler to build tests/horizon_ensemble_plan_harness.cpp")
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("horizon_ensemble_plan") / "harness")
+    # (-Wall -Werror: the header has to stay clean C++ for a compiler that knows nothing of HIP)
+    subprocess.run([_host_clang(), "-O1", "-std=c++17", "-Wall", "-Werror", "-o", exe,
+                    os.path.join(ROOT, "tests", "horizon_ensemble_plan_harness.cpp")], check=True)
+
+    def run(*args):
+        return subprocess.run([exe] + [a if isinstance(a, str) else str(int(a)) for a in args], check=True, capture_output=True,
+                              text=True).stdout.strip()
+    return run
+
+
+def _dims(shape):
+    S, Wn, Ws, Ww, ld, T, H1, H2, F = shape
+    FD, n_out, n_ord = S * Ws + Wn * Ww, (Wn + S * Wn if Wn else S), S * max(Wn, 1) + Wn
+    return FD, n_out, n_ord
+
+
+def _args(shape):
+    """the harness's 12 shape numbers as the engine's descriptor has them: weights read in the packed row (ldw = the layer's input
+    width), histories [rows][T][ldb] (hist_stride = T * ldb)"""
+    S, Wn, Ws, Ww, ld, T, H1, H2, F = shape
+    return (S, Wn, Ws, Ww, ld, T, H1, H2, F, H1, H2, T * ld)
+
+
+def _slices(harness, shape):
+    return dict(zip(BUFFERS, (int(v) for v in harness("slices", *_args(shape)).split())))
+
+
+def test_build_hashes_the_plan_header():
+    assert "horizon_ensemble_plan.h" in build.HEADERS
+    with open(os.path.join(build.CSRC, "horizon_ensemble_plan.h"), "rb") as f:
+        text = f.read()
+    # source_id is a hash over the listed headers' contents: the same files with one byte more give another id
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        csrc = os.path.join(tmp, "pkg", "csrc")
+        shutil.copytree(build.CSRC, csrc, ignore=shutil.ignore_patterns("*.o", "*.so", "*.key"))
+        shutil.copytree(os.path.join(ROOT, "include"), os.path.join(tmp, "include"))
+        assert build.source_id(csrc) == build.source_id()
+        with open(os.path.join(csrc, "horizon_ensemble_plan.h"), "wb") as f:
+            f.write(text + b"\n")
+        assert build.source_id(csrc) != build.source_id()
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_slice_sizes_are_what_the_single_model_engine_allocates(harness, shape):
+    """FusedRollout._setup's whole-horizon buffers for the same shape: rewards z(T, ld), hz_final z(FD, ld), hz_z1 z(H1, T, ld),
+    histories z(H1 | H2 | n_out | n_ord + Wn, T, ld), hz_dz z(dims[i + 1], T, ld); the state history is rows [0, FD) of hz_X z(F, T, ld).
+    The weight slices are the layers' own sizes: a model's packed row holds all five."""
+    S, Wn, Ws, Ww, ld, T, H1, H2, F = shape
+    FD, n_out, n_ord = _dims(shape)
+    s = _slices(harness, shape)
+    n = lambda *sh: int(torch.empty(*sh, device="meta").numel())   # noqa: E731
+    assert s["rewards"] == n(T, ld) and s["state_final"] == n(FD, ld)
+    assert s["z1_obs"] == s["h1_hist"] == s["dz1"] == n(H1, T, ld)
+    assert s["h2_hist"] == s["dz2"] == n(H2, T, ld)
+    assert s["logits_hist"] == s["dz3"] == n(n_out, T, ld)
+    assert s["orders_hist"] == n(n_ord + Wn, T, ld)
+    assert s["state_hist"] == n(FD, T, ld) <= n(F, T, ld)
+    assert (s["W1"], s["W2"], s["W3"], s["b2"], s["b3"]) == (H1 * F, H2 * H1, n_out * H2, H2, n_out)
+    dims = [F, H1, H2, n_out]
+    P = he.packed_count(dims)
+    assert P == sum(s[k] for k in ("W1", "W2", "W3", "b2", "b3")) + H1 and all(s[k] <= P for k in ("W1", "W2", "W3", "b2", "b3"))
+    # the library hands Python the header's numbers
+    d = _lib.NicHorizonDesc()
+    D = d.io.dims
+    D.n_scenarios, D.ldb, D.n_stores, D.n_warehouses, D.store_slots, D.warehouse_slots = min(ld, 72), ld, S, Wn, Ws, Ww
+    D.lost_demand = 1
+    d.T, d.H1, d.H2, d.n_out, d.ldw1, d.ldw2, d.ldw3, d.hist_stride = T, H1, H2, n_out, F, H1, H2, T * ld
+    keep = torch.zeros(8)   # (the validator wants non-null pointers; nothing is read through them without a launch)
+    for name in ("W1", "W2", "W3", "b2", "b3", "demand", "mask"):
+        setattr(d, name, keep.data_ptr())
+    for tab in (d.io.underage, d.io.holding, d.io.lead_times, d.io.wh_holding, d.io.wh_lead_times):
+        tab.p = keep.data_ptr()
+    assert hz.ensemble_slices(d) == s
+    d.head_mode, d.tape = 1, keep.data_ptr()
+    with pytest.raises(_lib.NicError, match="only head_mode 0"):
+        hz.ensemble_slices(d)
+
+
+def test_validator_accepts_and_refuses(harness):
+    shape = SHAPES[1]
+    s = _slices(harness, shape)
+
+    def fwd(n_models=3, head_mode=0, with_final=1, with_history=1, **kw):
+        st = {**s, **kw}
+        return int(harness("fwd", *_args(shape), head_mode, n_models, *[st[k] for k in BUFFERS], with_final, with_history).split()[0])
+
+    def bwd(n_models=3, head_mode=0, round_orders=0, **kw):
+        st = {**s, **kw}
+        return int(harness("bwd", *_args(shape), head_mode, round_orders, n_models, *[st[k] for k in BUFFERS]).split()[0])
+    (OK, MODELS, HEAD_MODE, ROUND, NEGATIVE, W1, W2, W3, B2, B3, Z1_OBS, REWARDS, FINAL, STATE_HIST, H1_HIST, H2_HIST, LOGITS_HIST,
+     ORDERS_HIST, DZ1, DZ2, DZ3, ALIGN) = range(22)
+    # accepted: the exact slices, one model, the most models, longer strides, one packed row behind all five weight pointers
+    assert fwd() == bwd() == OK
+    assert fwd(n_models=1) == bwd(n_models=1) == OK
+    assert fwd(n_models=65535) == bwd(n_models=65535) == OK
+    longer = {k: s[k] + 8 for k in BUFFERS}
+    assert fwd(**longer) == bwd(**longer) == OK
+    P = sum(s[k] for k in ("W1", "W2", "W3", "b2", "b3")) + 64
+    assert fwd(**{k: P for k in ("W1", "W2", "W3", "b2", "b3")}) == bwd(**{k: P for k in ("W1", "W2", "W3", "b2", "b3")}) == OK
+    assert fwd(W1=s["W1"] + 1, b3=s["b3"] + 3) == OK    # (weights are read as scalars: any stride >= the slice)
+    # model counts
+    for n in (0, -1, 65536):
+        assert fwd(n_models=n) == bwd(n_models=n) == MODELS
+    # the tape modes have no weights; rounded orders have no gradient
+    for mode in (1, 2):
+        assert fwd(head_mode=mode) == bwd(head_mode=mode) == HEAD_MODE
+    assert bwd(round_orders=1) == ROUND
+    # a negative stride, also of a buffer the call does not take
+    for k in BUFFERS:
+        assert fwd(**{k: -4}) == bwd(**{k: -4}) == NEGATIVE, k
+    assert fwd(with_history=0, state_hist=-4) == NEGATIVE
+    # every stride short of its slice
+    for k, code in (("W1", W1), ("W2", W2), ("W3", W3), ("b2", B2), ("b3", B3)):
+        assert fwd(**{k: s[k] - 1}) == bwd(**{k: s[k] - 1}) == code
+    assert fwd(z1_obs=s["z1_obs"] - 4) == Z1_OBS and fwd(rewards=s["rewards"] - 4) == REWARDS
+    assert fwd(state_final=s["state_final"] - 4) == FINAL and fwd(with_final=0, state_final=0) == OK
+    for k, code in zip(HISTORIES, (STATE_HIST, H1_HIST, H2_HIST, LOGITS_HIST, ORDERS_HIST)):
+        assert fwd(**{k: s[k] - 4}) == bwd(**{k: s[k] - 4}) == code
+        assert fwd(with_history=0, **{k: 0}) == OK            # evaluation: the history strides are not looked at
+    for k, code in (("dz1", DZ1), ("dz2", DZ2), ("dz3", DZ3)):
+        assert bwd(**{k: s[k] - 4}) == code
+        assert fwd(**{k: 0}) == OK                            # (the forward takes no dz buffers)
+    assert bwd(z1_obs=0, rewards=0, state_final=0) == OK      # (nor the backward these)
+    # 16-byte alignment of what the GEMMs and the reduction read next
+    for k in ALIGNED:
+        want_fwd = ALIGN if k not in ("dz1", "dz2", "dz3") else OK
+        want_bwd = ALIGN if k not in ("z1_obs", "rewards", "state_final") else OK
+        assert fwd(**{k: s[k] + 2}) == want_fwd and bwd(**{k: s[k] + 2}) == want_bwd, k
+    assert fwd(with_history=0, state_hist=s["state_hist"] + 2) == OK and fwd(with_final=0, state_final=s["state_final"] + 2) == OK
+    assert harness("fwd", *_args(shape), 0, 0, *[s[k] for k in BUFFERS], 1, 1) == "1 n_models must be 1..65535"
+    assert harness("bwd", *_args(shape), 0, 1, 3, *[s[k] for k in BUFFERS]) == "3 rounded orders have no gradient (evaluation only)"
+    assert harness("fwd", *_args(shape), 2, 3, *[s[k] for k in BUFFERS], 1, 1).startswith("2 only head_mode 0 (the MLP) has an ensemble form")
+    assert harness("fwd", *_args(shape), 0, 3, *[s[k] - (4 if k == "h2_hist" else 0) for k in BUFFERS], 1, 1) == \
+        "15 h2-history stride shorter than its slice"
+    assert harness("bwd", *_args(shape), 0, 0, 3, *[s[k] + (2 if k == "dz2" else 0) for k in BUFFERS]).startswith("21 the strides of z1_obs")
+    # the model offset is 64-bit: the last model of the largest ensemble on a 2^31-float slice
+    assert int(harness("offset", 65534, 2 ** 31)) == 65534 * 2 ** 31
+
+
+ENTRY_POINTS = {"nic_horizon_rollout_ensemble_fwd": 12, "nic_horizon_rollout_ensemble_bwd": 12, "nic_horizon_rollout_ensemble_slices": 2}
+C_TYPES = {"const NicHorizonDesc*": "LP_NicHorizonDesc", "const NicHorizonEnsemble*": "LP_NicHorizonEnsemble",
+           "NicHorizonEnsembleSlices*": "LP_NicHorizonEnsembleSlices", "float*": "c_void_p", "const float*": "c_void_p", "void*": "c_void_p",
+           "NicTable2": "NicTable2", "int64_t": "c_long", "int32_t": "c_int"}
+
+
+@pytest.mark.parametrize("name", sorted(ENTRY_POINTS))
+def test_entry_points_are_declared_and_bound_argument_for_argument(name):
+    with open(os.path.join(ROOT, "include", "nic_rollout.h")) as f:
+        header = f.read()
+    m = re.search(r"int %s\(([^)]*)\);" % name, header)
+    assert m, f"{name} is not declared in include/nic_rollout.h"
+    declared = [" ".join(a.split()).rsplit(" ", 1)[0] for a in m.group(1).split(",")]
+    res, args = _lib.PROTOTYPES[name]
+    assert res is _lib.C.c_int and len(args) == len(declared) == ENTRY_POINTS[name]
+    assert [C_TYPES[d] for d in declared] == [a.__name__ for a in args], (declared, args)
+    # the single-model calls' buffers, in their order, behind the descriptor and the ensemble
+    single = re.search(r"int %s\(([^)]*)\);" % name.replace("_ensemble", ""), header)
+    if single:
+        one = [" ".join(a.split()) for a in single.group(1).split(",")]
+        assert [" ".join(a.split()) for a in m.group(1).split(",")] == one[:1] + ["const NicHorizonEnsemble* e"] + one[1:]
+    with open(os.path.join(ROOT, "INTEGRATION.md")) as f:
+        assert name in f.read()
+    assert hasattr(_lib.load_library(), name)
+
+
+def test_declarations_cite_the_reference_lines_they_replace():
+    with open(os.path.join(ROOT, "include", "nic_rollout.h")) as f:
+        header = f.read()
+    for name in ("nic_horizon_rollout_ensemble_fwd", "nic_horizon_rollout_ensemble_bwd"):
+        comment = header[:header.index("int %s(" % name)].rsplit("/*", 1)[1]
+        assert "trainer.py:181-216" in comment and "once per model" in comment and "neural_networks.py:430-515" in comment, name
+
+
+def test_ctypes_structs_mirror_the_header():
+    with open(os.path.join(ROOT, "include", "nic_rollout.h")) as f:
+        header = f.read()
+    for cls in (_lib.NicHorizonEnsemble, _lib.NicHorizonEnsembleSlices):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (cls.__name__, cls.__name__), header, flags=re.S).group(1)
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        fields = []
+        for decl in body.split(";"):
+            decl = decl.strip()
+            if decl:
+                ctype, names = decl.split(None, 1)
+                fields += [(n.strip(), ctype) for n in names.split(",")]
+        want = {"int32_t": _lib.C.c_int32, "int64_t": _lib.C.c_int64}
+        assert [(n, want[t]) for n, t in fields] == list(cls._fields_)
+    assert tuple(n for n, _ in _lib.NicHorizonEnsembleSlices._fields_) == BUFFERS == hz.ENSEMBLE_BUFFERS
+    assert tuple(n for n, _ in _lib.NicHorizonEnsemble._fields_[2:]) == BUFFERS
+
+
+# ---- engine-side host logic ---------------------------------------------------------------------------------------------------------
+NAME = "f4_real_many_warehouses_data_driven"
+
+
+def _models(k, hidden=None, activation=None, policy=None, bias=True, materialize=True):
+    g = Golden(NAME)
+    c = g.fresh_config()
+
+    class _Sc:
+        problem_params = c["problem_params"]
+        store_params = {"demand": {"mean": [5.0]}}
+    nn_params = copy.deepcopy(c["nn_params"])
+    if hidden is not None:
+        nn_params["neurons_per_hidden_layer"]["master"] = hidden
+    if activation is not None:
+        nn_params["inner_layer_activations"]["master"] = activation
+    out = []
+    for i in range(k):
+        torch.manual_seed(100 + i)
+        m = NeuralNetworkCreator().create_neural_network(_Sc(), nn_params, device="cpu")
+        if materialize:
+            F = g.params["net.master.0.weight"].shape[1]
+            eng = he.FusedRollout.__new__(he.FusedRollout)
+            eng.model = m
+            eng.materialize(F)
+        out.append(m)
+    return out, g
+
+
+def test_packing_is_the_stack_of_the_single_model_packing():
+    models, g = _models(3)
+    lins = [m.master_linears() for m in models]
+    dims = [lins[0][0].in_features] + [lin.out_features for lin in lins[0]]
+    assert dims[0] == g.params["net.master.0.weight"].shape[1] and len(dims) == 4
+    want = torch.stack([sr.pack_weights(ls) for ls in lins])
+    assert want.shape == (3, he.packed_count(dims))
+    out = torch.full_like(want, float("nan"))
+    assert he.pack_ensemble_weights(lins, out) is out and torch.equal(out, want)
+    # nn.Linear's own order: per layer the weight, row-major, then the bias
+    for m, ls in enumerate(lins):
+        for lin, (o, n, k, bo) in zip(ls, he.layer_slices(dims)):
+            assert (n, k) == tuple(lin.weight.shape) and bo == o + n * k
+            assert torch.equal(out[m, o:bo].view(n, k), lin.weight.detach()) and torch.equal(out[m, bo:bo + n], lin.bias.detach())
+    assert he.layer_slices(dims)[-1][3] + dims[-1] == he.packed_count(dims)
+    with pytest.raises(ValueError):
+        he.pack_ensemble_weights(lins, torch.zeros(3, want.shape[1] + 1))
+
+
+def test_gradient_views_map_to_the_right_parameter_of_the_right_model():
+    """a [K][P] buffer filled with the packed weights themselves: every view must then equal its own parameter"""
+    models, _ = _models(3)
+    lins = [m.master_linears() for m in models]
+    dims = [lins[0][0].in_features] + [lin.out_features for lin in lins[0]]
+    P = he.packed_count(dims)
+    grad = torch.full((3, P + 6), float("nan"))
+    grad[:, :P] = he.pack_ensemble_weights(lins)
+    views = he.grad_views(grad, dims)
+    assert len(views) == 3
+    for ls, (gw, gb) in zip(lins, views):
+        assert len(gw) == len(gb) == len(ls) == 3
+        for lin, w, b in zip(ls, gw, gb):
+            assert w.shape == lin.weight.shape and b.shape == lin.bias.shape
+            assert torch.equal(w, lin.weight.detach()) and torch.equal(b, lin.bias.detach())
+            assert w.data_ptr() >= grad.data_ptr() and w._base is not None   # views, not copies
+
+
+def test_model_lists_that_are_refused_without_a_device():
+    good, _ = _models(2, materialize=False)
+    assert he.check_models(good) == good
+    with pytest.raises(ValueError, match="at least one"):
+        he.HorizonPolicyEnsemble([], {}, "cpu")
+    with pytest.raises(ValueError, match="at most 65,535"):
+        he.check_models(good[:1] * 65536)
+    narrow, _ = _models(1, hidden=[32, 16], materialize=False)
+    with pytest.raises(ValueError, match=r"model 1: layer sizes \[32, 16, 66\] differ from model 0's \[32, 32, 66\]"):
+        he.HorizonPolicyEnsemble(good[:1] + narrow, {}, "cpu")
+    relu, _ = _models(1, activation="relu", materialize=False)   # not FusedRollout's either
+    with pytest.raises(ValueError, match="model 1: HorizonPolicyEnsemble handles the data_driven policy"):
+        he.HorizonPolicyEnsemble(good[:1] + relu, {}, "cpu")
+    with pytest.raises(ValueError, match="model 0"):
+        he.HorizonPolicyEnsemble([torch.nn.Linear(4, 1)], {}, "cpu")
+    vanilla = Golden("cfg1_one_store_lost_vanilla")
+    cv = vanilla.fresh_config()
+
+    class _Sc:
+        problem_params = cv["problem_params"]
+        store_params = {"demand": {"mean": [5.0]}}
+    other = NeuralNetworkCreator().create_neural_network(_Sc(), cv["nn_params"], device="cpu")
+    with pytest.raises(ValueError, match="model 1: .*got 'vanilla_one_store'"):
+        he.HorizonPolicyEnsemble(good[:1] + [other], {}, "cpu")
+    nobias, _ = _models(1, materialize=False)
+    nobias[0].master_linears()[1].bias = None
+    with pytest.raises(ValueError, match="model 1: a layer without bias"):
+        he.HorizonPolicyEnsemble(good[:1] + nobias, {}, "cpu")
