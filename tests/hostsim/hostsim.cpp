@@ -86,6 +86,19 @@ int hostsim_head_data_driven(const float* Z, const float* wh, const float* mask,
         }
     return 0;
 }
+// the two directions on their own, as the device launches them (tests/kernel_checks.py: check_data_driven_head)
+int hostsim_head_data_driven_fwd(const float* Z, const float* wh, const float* mask, float* so, float* wo, int32_t S, int32_t Wn,
+                                 int32_t Ww, int32_t B, int32_t ldb) {
+    for (int64_t b = 0; b < B; ++b)
+        for (int w = 0; w < Wn; ++w) nic::head_data_driven_fwd_one(Z, wh, mask, so, wo, S, Wn, Ww, ldb, b, w);
+    return 0;
+}
+int hostsim_head_data_driven_bwd(const float* Z, const float* wh, const float* mask, const float* g_so, const float* g_wo, float* dZ,
+                                 float* g_wh, int32_t S, int32_t Wn, int32_t Ww, int32_t B, int32_t ldb) {
+    for (int64_t b = 0; b < B; ++b)
+        for (int w = 0; w < Wn; ++w) nic::head_data_driven_bwd_one(Z, wh, mask, g_so, g_wo, dZ, g_wh, S, Wn, Ww, ldb, b, w);
+    return 0;
+}
 int hostsim_env_step_fwd(const NicEnvStepIO* io, float* so, float* wo, float* eo, float* r) {
     fwd_all<NIC_MAX_SLOTS>(*io, so, wo, eo, r);
     return 0;

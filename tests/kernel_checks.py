@@ -4,7 +4,13 @@ The same checks run against two builds of the same NIC_HD bodies:
   * HostSimBackend — tests/hostsim (g++), CPU tensors, runs on the CPU container (`-m "not gpu"`);
   * HipBackend     — the product library libnic_hip.so through the C ABI, device tensors (`-m gpu`).
 Expected values come from the golden fixtures (reference outputs) and the oracle's autograd.
+The data_driven, serial and softplus heads also have fixed edge-case tables against float64 (second half of this file; the shared
+helpers - input families, referee bound, padding checks - serve tests/glue_checks.py too).
 """
+import functools
+import zlib
+from collections import namedtuple
+
 import torch
 import torch.nn.functional as F
 
@@ -50,6 +56,18 @@ class HostSimBackend:
     def head_serial_bwd(self, Z, wh, ech, ub, gso, gwo, geo, dZ, gwi, gei, E, Ww, We, B, ldb):
         self.h.hostsim_head_serial_bwd(P(Z), P(wh), P(ech), ub, P(gso), P(gwo), P(geo), P(dZ), P(gwi), P(gei), E, Ww, We, B, ldb)
 
+    # (Wn >= 1: the one-store form of this head, Wn == 0, lives in the device kernel and has no NIC_HD body)
+    def head_data_driven_fwd(self, Z, wh, mask, so, wo, S, Wn, Ww, B, ldb):
+        assert Wn > 0
+        self.h.hostsim_head_data_driven_fwd(P(Z), P(wh), P(mask), P(so), P(wo), S, Wn, Ww, B, ldb)
+
+    def head_data_driven_bwd(self, Z, wh, mask, gso, gwo, dZ, gwh, S, Wn, Ww, B, ldb):
+        assert Wn > 0
+        self.h.hostsim_head_data_driven_bwd(P(Z), P(wh), P(mask), P(gso), P(gwo), P(dZ), P(gwh), S, Wn, Ww, B, ldb)
+
+    def last_kernel(self):
+        return None
+
 
 class HipBackend:
     device = "cuda"
@@ -91,6 +109,15 @@ class HipBackend:
     def head_serial_bwd(self, Z, wh, ech, ub, gso, gwo, geo, dZ, gwi, gei, E, Ww, We, B, ldb):
         _lib.check(self.l.nic_head_serial_bwd(P(Z), P(wh), P(ech), ub, P(gso), P(gwo), P(geo), P(dZ), P(gwi), P(gei), E, Ww,
                                               We, B, ldb, self._s()))
+
+    def head_data_driven_fwd(self, Z, wh, mask, so, wo, S, Wn, Ww, B, ldb):
+        _lib.check(self.l.nic_head_data_driven_fwd(P(Z), P(wh), P(mask), P(so), P(wo), S, Wn, Ww, B, ldb, self._s()))
+
+    def head_data_driven_bwd(self, Z, wh, mask, gso, gwo, dZ, gwh, S, Wn, Ww, B, ldb):
+        _lib.check(self.l.nic_head_data_driven_bwd(P(Z), P(wh), P(mask), P(gso), P(gwo), P(dZ), P(gwh), S, Wn, Ww, B, ldb, self._s()))
+
+    def last_kernel(self):
+        return self.l.nic_last_kernel().decode()
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -481,3 +508,373 @@ def _referee_adjacency(S, Wn):
 WAREHOUSE_HEAD_REFEREE_B = 150
 WAREHOUSE_HEAD_REFEREE_CASES = [(S, Wn, _referee_adjacency(S, Wn)) for S, Wn in
                                 ((21, 9), (17, 12), (32, 4), (5, 32), (64, 17), (70, 2), (1, 5))]
+
+
+# ---- the elementwise heads at their edges (data_driven, serial, softplus): fixed tables, float64 references ------------------------
+# Two input families ("Glue kernels at their edges").  GRID: logits / quantities multiples of 1/8 of a few units with
+# 25 % exact zeros, incoming gradients multiples of 1/4, the stock of a proportional allocation = sum * f with f cycling over
+# ALLOC_FACTORS per scenario and every 7th scenario all-zero with stock 2 - every float32 sum is exact in any order, the ratio is f
+# bit for bit (a real tie at f == 1), so the forward has to EQUAL the float64 reference rounded to float32.  RANDOM: Gaussian logits,
+# uniform quantities, the stock factor drawn from [0, 0.9] u [1.1, 3]; judged by the referee bound of HEAD_REFEREE_C.
+# No scenario is excluded in either family.
+EPS32 = float(torch.tensor(1e-10, dtype=torch.float32))   # the `+ 1e-10` of a float32 expression adds the float32 value of 1e-10
+ALLOC_FACTORS = (0.0, 0.25, 0.5, 1.0, 1.5, 3.0)
+PREFILL = 0.75          # what accumulating outputs hold before the launch (the increment is compared)
+NAN = float("nan")      # what fully written outputs hold before the launch
+B_LANES64 = (1, 63, 64, 65, 130)       # one lane, a ragged / full / just-started second workgroup, a ragged third
+B_LANES256 = (1, 255, 256, 257, 600)
+REFEREE_FIGURES = {}    # (backend, kernel, tensor) -> worst max|kernel - fp64| / max|torch fp32 - fp64| seen in this session
+
+
+def out_ld(B):
+    """a leading dimension with at least one padding column behind B scenarios"""
+    return (B // 32 + 1) * 32
+
+
+def grid_values(gen, shape, lo, hi, step=8):
+    """uniform on {lo, lo + 1/step, ..., hi}"""
+    return torch.randint(int(lo * step), int(hi * step) + 1, shape, generator=gen).float() / step
+
+
+def stock_factors(gen, B):
+    """[0, 0.9) u [1.1, 3): nothing near the kink of clamp(max = 1)"""
+    u = torch.rand(B, generator=gen, dtype=torch.float64)
+    return torch.where(u < 0.5, 1.8 * u, 1.1 + (u - 0.5) * 3.8)
+
+
+def soa(t, ld, dev, fill=0.0):
+    """[..., B] -> [..., ld] on `dev` (padding columns = fill)"""
+    out = torch.full(tuple(t.shape[:-1]) + (ld,), fill, dtype=torch.float32)
+    out[..., :t.shape[-1]] = t
+    return out.to(dev)
+
+
+def filled(shape, value, dev):
+    return torch.full(shape, value, dtype=torch.float32, device=dev)
+
+
+def same_bits(a, b):
+    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+def padding_untouched(buf, before, first, what):
+    """columns [first, ldb) hold bit for bit what they held before the launch"""
+    assert same_bits(buf[..., first:], before[..., first:]), (what, "padding columns written")
+
+
+RAN_KERNELS = set()     # every name nic_last_kernel() gave a check of this session
+
+
+def kernel_is(be, want, what):
+    got = be.last_kernel()
+    assert got is None or got == want, (what, got, want)
+    RAN_KERNELS.add(got)
+
+
+def referee(be, kernel, tensor, got, ref32, ref64, c, what):
+    """max|kernel - fp64| <= c * max|torch fp32 - fp64| + one ulp of the tensor's largest magnitude; records and prints the ratio"""
+    got, ref32, ref64 = got.detach(), ref32.detach(), ref64.detach()
+    err_k = float((got.double() - ref64).abs().max()) if got.numel() else 0.0
+    err_t = float((ref32.double() - ref64).abs().max()) if got.numel() else 0.0
+    ulp = _ulp(ref64.abs().max()) if got.numel() else 0.0
+    ratio = err_k / err_t if err_t > 0 else (0.0 if err_k == 0 else float("inf"))
+    key = (type(be).__name__, kernel, tensor)
+    if ratio != float("inf"):
+        REFEREE_FIGURES[key] = max(REFEREE_FIGURES.get(key, 0.0), ratio)
+    print(f"referee {what} {key[0]} {kernel} {tensor}: kernel {err_k:.3e} torch32 {err_t:.3e} ratio {ratio:.2f} ulp {ulp:.1e} c {c}")
+    assert err_k <= c * err_t + ulp, (what, kernel, tensor, "kernel", err_k, "torch32", err_t, "ulp", ulp, "c", c)
+    return ratio
+
+
+def serial_sum32(rows):
+    """float32 sum of the rows in order, one add at a time (what a lane does)"""
+    s = torch.zeros_like(rows[0], dtype=torch.float32)
+    for r in rows:
+        s = s + r.float()
+    return s
+
+
+def assert_grid_allocation(sum64, rows, ratio64, factors, zero_scn, what):
+    """The grid family's conditions, on the reference alone: float32 sums exact in any order, sum + 1e-10f == sum, the ratio equal
+    to f bit for bit wherever the sum is positive, and nothing but real ties closer to the kink than 0.5."""
+    rows = list(rows)
+    for order in (rows, rows[::-1]):
+        assert torch.equal(serial_sum32(order).double(), sum64), (what, "a float32 sum of the grid family is not exact")
+    pos = sum64 > 0
+    s32 = sum64.float()
+    assert torch.equal((s32 + torch.tensor(EPS32))[pos], s32[pos]), (what, "sum + 1e-10f != sum")
+    f = factors.expand_as(sum64)
+    live = pos & ~zero_scn.expand_as(sum64)
+    assert torch.equal(ratio64.float()[live], f.float()[live]), (what, "ratio != f")
+    dist = (ratio64.float().double() - 1).abs()
+    assert bool(((dist == 0) | (dist >= 0.5)).all()), (what, "a scenario near the kink")
+    assert bool((ratio64[live & (f == 1)] < 1).all()), (what, "the float64 ratio of a tie must sit just below 1")
+
+
+# -- data_driven head
+DataDrivenCase = namedtuple("DataDrivenCase", "id family S Wn Ww B masked")
+
+
+def _data_driven_table():
+    t = []
+    # S below / at / beyond kHeadBatch = 8 and its first two multiples, 64, 70; Wn in 1, 2, 5; Ww in 1, 4, 16; every batch edge
+    for i, S in enumerate((1, 7, 8, 9, 15, 16, 17, 23, 24, 25, 64, 70)):
+        Wn, Ww = (1, 2, 5)[i % 3], (1, 4, 16)[(i + 1) % 3]
+        t.append(DataDrivenCase(f"grid-S{S}-Wn{Wn}-Ww{Ww}", "grid", S, Wn, Ww, B_LANES64[i % 5], Wn - 1 if Wn > 1 else -1))
+        Wn, Ww = (2, 5, 1)[i % 3], (4, 16, 1)[(i + 1) % 3]
+        t.append(DataDrivenCase(f"random-S{S}-Wn{Wn}-Ww{Ww}", "random", S, Wn, Ww, B_LANES64[(i + 2) % 5], Wn - 1 if Wn > 2 else -1))
+    t.append(DataDrivenCase("grid-S9-Wn1-all-masked", "grid", 9, 1, 4, 65, 0))     # the only warehouse serves nobody
+    for B in B_LANES64:                                                           # one-store settings: orders = relu(Z)
+        t.append(DataDrivenCase(f"grid-S{1 + B % 4}-Wn0-B{B}", "grid", 1 + B % 4, 0, 1, B, -1))
+    t.append(DataDrivenCase("random-S9-Wn0", "random", 9, 0, 1, 130, -1))
+    assert len({c.id for c in t}) == len(t)
+    return t
+
+
+DATA_DRIVEN_CASES = _data_driven_table()
+
+
+def _data_driven_expression(p, dtype):
+    """DataDrivenNet.forward's tail (neural_networks.py:474-515 + :111-138) in aten ops + autograd, in `dtype`"""
+    c = p["case"]
+    z = p["Z"].to(dtype).requires_grad_(True)
+    out = torch.relu(z)
+    if c.Wn == 0:
+        (out * p["g_so"].to(dtype)).sum().backward()
+        return {"so": out.detach(), "dZ": z.grad}
+    w = p["wh"].to(dtype).requires_grad_(True)
+    alloc = out[c.Wn:].reshape(c.S, c.Wn, c.B) * p["mask"].to(dtype)[:, :, None]
+    total = alloc.sum(dim=0)
+    ratio = w.sum(dim=1) / (total + EPS32)
+    so = (alloc * torch.clamp(ratio, max=1.0)[None]).reshape(c.S * c.Wn, c.B)
+    ((so * p["g_so"].to(dtype)).sum() + (out[:c.Wn] * p["g_wo"].to(dtype)).sum()).backward()
+    return {"so": so.detach(), "wo": out[:c.Wn].detach(), "dZ": z.grad, "g_wh": w.grad, "ratio": ratio.detach(), "sum": total.detach(),
+            "alloc": alloc.detach()}
+
+
+@functools.lru_cache(maxsize=None)
+def data_driven_problem(c):
+    """inputs of a case (CPU, [rows][B]) and the float64 / float32 references; computed once, never modified"""
+    gen = torch.Generator().manual_seed(zlib.crc32(c.id.encode()))
+    S, Wn, Ww, B = c.S, c.Wn, c.Ww, c.B
+    nW, rows = max(Wn, 1), Wn + S * max(Wn, 1)
+    b = torch.arange(B)
+    zero_scn = b % 7 == 6
+    p = {"case": c}
+    mask = (torch.rand(S, nW, generator=gen) < 0.7).float()
+    mask[0] = 1.0
+    if c.masked >= 0:
+        mask[:, c.masked] = 0.0
+    if c.family == "grid":
+        Z = grid_values(gen, (rows, B), -3, 3)
+        zeros = torch.rand(rows, B, generator=gen) < 0.25
+        Z[zeros] = 0.0
+        Z[zeros & (torch.rand(rows, B, generator=gen) < 0.5)] = -0.0
+        Z[Wn:, zero_scn] = -Z[Wn:, zero_scn].abs()                  # every 7th scenario: no store asks for anything
+        g_so, g_wo = grid_values(gen, (S * nW, B), -2, 2, 4), grid_values(gen, (nW, B), -2, 2, 4)
+    else:
+        Z = torch.randn(rows, B, generator=gen) * 2
+        g_so, g_wo = torch.randn(S * nW, B, generator=gen), torch.randn(nW, B, generator=gen)
+    p.update(Z=Z, mask=mask, g_so=g_so, g_wo=g_wo)
+    if Wn:
+        total = (torch.relu(Z[Wn:]).reshape(S, Wn, B) * mask[:, :, None]).double().sum(dim=0)     # [Wn][B]
+        if c.family == "grid":
+            factors = torch.tensor(ALLOC_FACTORS, dtype=torch.float64)[b % 6]
+            target = total * factors
+            target[:, zero_scn] = 2.0
+            if c.masked >= 0:                                       # a warehouse that serves nobody: with stock, and without
+                target[c.masked] = torch.where(b % 2 == 0, 2.0, 0.0).double()
+            wh = grid_values(gen, (Wn, Ww, B), 0, 2).double()
+            wh[:, 0] = target - wh[:, 1:].sum(dim=1)
+            p["wh"] = wh.float()
+            assert torch.equal(p["wh"].double(), wh)
+            for order in (range(Ww), range(Ww - 1, -1, -1)):
+                assert torch.equal(serial_sum32([p["wh"][:, k] for k in order]).double(), target), (c.id, "pipeline total not exact")
+        else:
+            wh = torch.rand(Wn, Ww, B, generator=gen, dtype=torch.float64) + 0.05
+            wh = wh * (stock_factors(gen, B) * total / wh.sum(dim=1))[:, None]
+            p["wh"] = wh.float()
+    p["ref64"], p["ref32"] = _data_driven_expression(p, torch.float64), _data_driven_expression(p, torch.float32)
+    if Wn and c.family == "grid":
+        r = p["ref64"]
+        live_w = torch.ones(Wn, 1, dtype=torch.bool)
+        if c.masked >= 0:
+            live_w[c.masked] = False
+        members = [r["alloc"][s] for s in range(S)]
+        assert_grid_allocation(r["sum"], members, r["ratio"], factors[None], zero_scn[None] | ~live_w, c.id)
+        assert torch.equal(r["so"].float().double() * 32, (r["so"].float().double() * 32).round()), (c.id, "orders off the 1/32 grid")
+    return p
+
+
+def data_driven_planted(c):
+    """which of the planted situations a grid case really contains"""
+    p = data_driven_problem(c)
+    Z, out = p["Z"], {}
+    neg_zero = (Z == 0) & torch.signbit(Z)
+    out["logit_plus_zero"], out["logit_minus_zero"] = bool(((Z == 0) & ~neg_zero).any()), bool(neg_zero.any())
+    if c.Wn:
+        r = p["ref64"]
+        out["tie"] = bool((r["ratio"].float() == 1).any())
+        out["all_zero_with_stock"] = bool(((r["sum"] == 0) & (r["ratio"] > 1)).any())
+        if c.masked >= 0:
+            tot = p["wh"][c.masked].double().sum(dim=0)
+            out["masked_with_stock"], out["masked_without_stock"] = bool((tot > 0).any()), bool((tot == 0).any())
+    return out
+
+
+def check_data_driven_head(be, c):
+    """nic_head_data_driven_fwd / _bwd (or the host build of their bodies) on one case of DATA_DRIVEN_CASES"""
+    p = data_driven_problem(c)
+    dev, S, Wn, Ww, B = be.device, c.S, c.Wn, c.Ww, c.B
+    nW, ld = max(Wn, 1), out_ld(B)
+    r64, r32 = p["ref64"], p["ref32"]
+    Z, mask = soa(p["Z"], ld, dev), (p["mask"].contiguous().to(dev) if Wn else None)
+    wh = soa(p["wh"], ld, dev) if Wn else None
+    so, wo = filled((S * nW, ld), NAN, dev), (filled((Wn, ld), NAN, dev) if Wn else None)
+    before = [so.clone(), wo.clone() if Wn else None]
+    be.head_data_driven_fwd(Z, wh, mask, so, wo, S, Wn, Ww, B, ld)
+    be.sync()
+    kernel_is(be, "head_data_driven_fwd_kernel", c.id)
+    padding_untouched(so, before[0], B, (c.id, "store orders"))
+    got_so = so[:, :B].cpu()
+    assert bool((got_so[r64["so"] == 0] == 0).all()), (c.id, "a structurally zero store order is not an exact zero")
+    if Wn:
+        padding_untouched(wo, before[1], B, (c.id, "warehouse orders"))
+        assert torch.equal(wo[:, :B].cpu(), torch.relu(p["Z"][:Wn])), (c.id, "the warehouse's own order passes through the ReLU only")
+    if c.family == "grid" or Wn == 0:
+        assert torch.equal(got_so, r64["so"].float()), (c.id, "store orders", int((got_so != r64["so"].float()).sum()))
+    else:
+        referee(be, "head_data_driven_fwd", "store_orders", got_so, r32["so"], r64["so"], HEAD_REFEREE_C["wide"], c.id)
+    dZ = filled((p["Z"].shape[0], ld), NAN, dev)
+    g_wh = filled((Wn, Ww, ld), PREFILL, dev) if Wn else None
+    before = [dZ.clone(), g_wh.clone() if Wn else None]
+    be.head_data_driven_bwd(Z, wh, mask, soa(p["g_so"], ld, dev), soa(p["g_wo"], ld, dev) if Wn else None, dZ, g_wh, S, Wn, Ww, B, ld)
+    be.sync()
+    kernel_is(be, "head_data_driven_bwd_kernel", c.id)
+    padding_untouched(dZ, before[0], B, (c.id, "dZ"))
+    got_dZ = dZ[:, :B].cpu()
+    dead = p["Z"] <= 0
+    if Wn:
+        dead[Wn:] |= (p["mask"] == 0)[:, :, None].expand(S, Wn, B).reshape(S * Wn, B)
+    assert bool((got_dZ[dead] == 0).all()), (c.id, "dZ of a logit <= 0 (or of a masked pair) is not an exact zero")
+    if Wn == 0:
+        assert torch.equal(got_dZ, r64["dZ"].float()), (c.id, "dZ")
+        return
+    referee(be, "head_data_driven_bwd", "dZ", got_dZ, r32["dZ"], r64["dZ"], HEAD_REFEREE_C["wide"], c.id)
+    padding_untouched(g_wh, before[1], B, (c.id, "g_wh"))
+    inc = g_wh[:, :, :B].cpu().double() - PREFILL
+    inc32 = (r32["g_wh"] + torch.tensor(PREFILL)).double() - PREFILL       # the same float32 add into the same prefill
+    referee(be, "head_data_driven_bwd", "g_wh", inc, inc32, r64["g_wh"], HEAD_REFEREE_C["wide"], c.id)
+
+
+# -- serial head
+SerialCase = namedtuple("SerialCase", "id E Ww We B")
+SERIAL_CASES = [SerialCase(f"E{E}-Ww{Ww}-We{We}-B{B}", E, Ww, We, B) for E, Ww, We, B in
+                ((0, 2, 2, 1), (0, 5, 2, 65), (0, 2, 5, 130), (1, 2, 5, 63), (1, 5, 2, 64), (1, 5, 5, 1), (3, 2, 2, 65), (3, 5, 5, 130),
+                 (3, 2, 5, 64), (3, 5, 2, 63))]
+SERIAL_EXTREMES = (40.0, -40.0, 100.0, -100.0, 0.0, -0.0)     # the sigmoid saturates; expf(100) = inf on one side
+
+
+def _serial_expression(p, dtype):
+    c = p["case"]
+    z, wh = p["Z"].to(dtype).requires_grad_(True), p["wh"].to(dtype).requires_grad_(True)
+    ech = p["ech"].to(dtype).requires_grad_(True)
+    up = torch.cat((torch.full((1, c.B), p["ub"], dtype=dtype), ech[:, 0], wh[:, 0]), dim=0)   # neural_networks.py:335-344
+    alloc = torch.sigmoid(z) * up
+    (alloc * p["g"].to(dtype)).sum().backward()
+    g_ech = ech.grad if ech.grad is not None else torch.zeros_like(ech)
+    return {"orders": alloc.detach(), "dZ": z.grad, "g_wh_inv": wh.grad, "g_ech_inv": g_ech}
+
+
+@functools.lru_cache(maxsize=None)
+def serial_problem(c):
+    gen = torch.Generator().manual_seed(zlib.crc32(c.id.encode()))
+    E, B = c.E, c.B
+    Z = torch.randn(E + 2, B, generator=gen) * 2
+    for k, v in enumerate(SERIAL_EXTREMES):
+        for j in range(E + 2):
+            Z[j, (3 * k + 5 * j) % B] = v if B > 1 else SERIAL_EXTREMES[(j + E) % 4]
+    p = {"case": c, "Z": Z, "ub": 20.0, "wh": torch.rand(1, c.Ww, B, generator=gen) * 9, "ech": torch.rand(E, c.We, B, generator=gen) * 9,
+         "g": torch.randn(E + 2, B, generator=gen)}
+    p["ref64"], p["ref32"] = _serial_expression(p, torch.float64), _serial_expression(p, torch.float32)
+    return p
+
+
+def check_serial_head_case(be, c):
+    p = serial_problem(c)
+    dev, E, Ww, We, B = be.device, c.E, c.Ww, c.We, c.B
+    ld, quad = out_ld(B), HEAD_REFEREE_C["quad"]
+    r64, r32 = p["ref64"], p["ref32"]
+    Z, wh = soa(p["Z"], ld, dev), soa(p["wh"], ld, dev)
+    ech = soa(p["ech"], ld, dev) if E else None
+    so, wo, eo = filled((1, 1, ld), NAN, dev), filled((1, ld), NAN, dev), (filled((E, ld), NAN, dev) if E else None)
+    before = [x.clone() if x is not None else None for x in (so, wo, eo)]
+    be.head_serial_fwd(Z, wh, ech, p["ub"], so, wo, eo, E, Ww, We, B, ld)
+    be.sync()
+    kernel_is(be, "head_serial_fwd_kernel", c.id)
+    for x, b4, what in zip((so, wo, eo), before, ("store", "warehouse", "echelon")):
+        if x is not None:
+            padding_untouched(x, b4, B, (c.id, what, "orders"))
+    got = torch.cat(([eo[:, :B]] if E else []) + [wo[:, :B], so[0, :, :B]], dim=0).cpu()
+    referee(be, "head_serial_fwd", "orders", got, r32["orders"], r64["orders"], quad, c.id)
+    dZ, gwi = filled((E + 2, ld), NAN, dev), filled((1, Ww, ld), PREFILL, dev)
+    gei = filled((E, We, ld), PREFILL, dev) if E else None
+    before = [x.clone() if x is not None else None for x in (dZ, gwi, gei)]
+    g = soa(p["g"], ld, dev)
+    be.head_serial_bwd(Z, wh, ech, p["ub"], g[E + 1:], g[E:E + 1], g[:E] if E else None, dZ, gwi, gei, E, Ww, We, B, ld)
+    be.sync()
+    kernel_is(be, "head_serial_bwd_kernel", c.id)
+    for x, b4, what in zip((dZ, gwi, gei), before, ("dZ", "g_wh_inv", "g_ech_inv")):
+        if x is not None:
+            padding_untouched(x, b4, B, (c.id, what))
+    referee(be, "head_serial_bwd", "dZ", dZ[:, :B].cpu(), r32["dZ"], r64["dZ"], quad, c.id)
+    for name, buf, b4 in (("g_wh_inv", gwi, before[1]), ("g_ech_inv", gei, before[2])):
+        if buf is None:
+            continue
+        assert same_bits(buf[:, 1:], b4[:, 1:]), (c.id, name, "a pipeline slot behind the on-hand one was written")
+        inc = buf[:, :, :B].cpu().double() - PREFILL
+        inc32 = (r32[name] + torch.tensor(PREFILL)).double() - PREFILL
+        referee(be, "head_serial_bwd", name, inc, inc32, r64[name], quad, c.id)
+
+
+# -- softplus head: the project's relative band with NO absolute term (the small orders at z << 0 keep their relative accuracy:
+#    softplus(-79) = 4.9e-35 is still a normal float32)
+SOFTPLUS_RTOL = 3e-6
+SoftplusCase = namedtuple("SoftplusCase", "id rows B")
+SOFTPLUS_CASES = [SoftplusCase(f"rows{r}-B{B}", r, B) for r, B in ((1, 1), (5, 255), (33, 256), (1, 257), (5, 600), (33, 1), (1, 600),
+                                                                   (5, 1), (33, 257))]
+SOFTPLUS_Z = (-80.0, -40.0, -16.0, 0.0, -0.0, 18.9, 19.0, 19.1, 30.0)     # 18.9 / 19 / 19.1 straddle the threshold z + 1 = 20
+
+
+@functools.lru_cache(maxsize=None)
+def softplus_problem(c):
+    gen = torch.Generator().manual_seed(zlib.crc32(c.id.encode()))
+    n = c.rows * c.B
+    Z = torch.linspace(-30, 30, n) if n > 1 else torch.tensor([SOFTPLUS_Z[0]])
+    special = torch.tensor(SOFTPLUS_Z)
+    Z[:min(n, len(special))] = special[:n]
+    Z = Z.reshape(c.rows, c.B).clone()
+    g = (1 + torch.rand(c.rows, c.B, generator=gen)) * torch.where(torch.rand(c.rows, c.B, generator=gen) < 0.5, -1.0, 1.0)
+    z64 = Z.double().requires_grad_(True)
+    y = F.softplus(z64 + 1)
+    (y * g.double()).sum().backward()
+    return {"case": c, "Z": Z, "g": g, "y": y.detach(), "dZ": z64.grad}
+
+
+def check_softplus_head_case(be, c):
+    p = softplus_problem(c)
+    dev, rows, B = be.device, c.rows, c.B
+    ld = out_ld(B)
+    Z, g = soa(p["Z"], ld, dev), soa(p["g"], ld, dev)
+    out, dZ = filled((rows, ld), NAN, dev), filled((rows, ld), NAN, dev)
+    before = out.clone()
+    be.head_softplus_fwd(Z, out, rows, B, ld)
+    be.sync()
+    kernel_is(be, "head_softplus_fwd_kernel", c.id)
+    be.head_softplus_bwd(Z, g, dZ, rows, B, ld)
+    be.sync()
+    kernel_is(be, "head_softplus_bwd_kernel", c.id)
+    padding_untouched(out, before, B, (c.id, "orders"))
+    padding_untouched(dZ, before, B, (c.id, "dZ"))
+    torch.testing.assert_close(out[:, :B].cpu().double(), p["y"], rtol=SOFTPLUS_RTOL, atol=0, msg=lambda m: f"{c.id} orders: {m}")
+    torch.testing.assert_close(dZ[:, :B].cpu().double(), p["dZ"], rtol=SOFTPLUS_RTOL, atol=0, msg=lambda m: f"{c.id} dZ: {m}")
