@@ -206,6 +206,42 @@ int nic_linear_bwd_thin(const float* W, int64_t ldw, const float* dY, const floa
 int nic_wgrad_reduce(const float* slab, int64_t lds, int32_t n_splits, float* dW, int64_t lddw, float* db,
                      int32_t N, int32_t K, float scale, void* stream);
 
+/* ---- the same three GEMM calls for n_models models in ONE launch each (grid y = model) --------------------------------
+ * Model m's copy of each operand starts m x its stride (in floats) behind model 0's; the kernels advance their pointers once,
+ * at entry, by a 64-bit blockIdx.y * stride and then run the single-model kernel's instruction stream.  The launch plan is the
+ * single-model entry point's for model 0's operands (the same kernel, grid x, n_splits and operand-eligibility bits), so model
+ * m's outputs are the bits of nic_linear_fwd / nic_linear_wgrad / nic_wgrad_reduce called on its slice.  nic_last_kernel():
+ * the single-model kernel's name with ",models=K>" in place of the closing ">" (the two reduce kernels, which have no
+ * template list: ",models=K" appended).
+ * Strides: 1 <= n_models <= 65535; none negative; an output stride covers one model's slice (Y: N * ldb, slab: n_splits * N *
+ * lds, dW: (N-1) * lddw + K, db: N), an input stride too (W: (N-1) * ldw + K, bias: N, X: K * ldb, dY: N * ldb) - except that
+ * the forward takes X_stride = 0: one input shared by all models; the strides of W, X, Y, dY and the slab are multiples of 4
+ * floats (every model's operands pass model 0's 16-byte test); the bias, dW and db strides are free (scalar accesses).
+ * Coverage: what the whole-horizon route of the data_driven policy asks for - forwards of N <= 64 rows, one-period weight
+ * gradients of N <= 128 on the small and the register-staged kernels.  A request whose plan picks another kernel (the 128 x 128
+ * and larger LDS-DMA tiles), a bad stride and every argument error of the single-model call are refused: non-zero status, the
+ * reason (csrc/linear_models_plan.h) in nic_last_error(), nothing launched.
+ *
+ * nic_linear_fwd_models replaces nn.Linear + activation inside MyNeuralNetwork.create_sequential_net
+ * (neural_networks.py:80-106), once per model. */
+int nic_linear_fwd_models(const float* W, int64_t ldw, int64_t W_stride, const float* bias /* may be NULL */, int64_t bias_stride,
+                          const float* X, int64_t X_stride, float* Y, int64_t Y_stride, int32_t N, int32_t K,
+                          int32_t n_scenarios, int32_t ldb, int32_t act, int32_t n_models, void* stream);
+/* nic_linear_wgrad for n_models models: autograd's weight / bias gradient of the same layer (neural_networks.py:80-106 under
+ * `backward`, trainer.py:177), once per model.  slab: [n_models][n_splits][N][lds] with slab_stride between models. */
+int nic_linear_wgrad_models(const float* dY, int64_t dY_stride, const float* X, int64_t X_stride, float* slab,
+                            int64_t slab_stride, int64_t lds, int32_t N, int32_t K, int32_t n_scenarios, int32_t ldb,
+                            int32_t n_splits, int32_t n_models, void* stream);
+/* nic_wgrad_reduce for n_models models (the reduction at the end of the same gradient, neural_networks.py:80-106 under
+ * `backward`, once per model): model m's dW / db may be rows of one packed [n_models][P] gradient buffer (strides P). */
+int nic_wgrad_reduce_models(const float* slab, int64_t slab_stride, int64_t lds, int32_t n_splits, float* dW, int64_t lddw,
+                            int64_t dW_stride, float* db /* may be NULL */, int64_t db_stride, int32_t N, int32_t K,
+                            float scale, int32_t n_models, void* stream);
+/* 1 if the model forms take a layer as the engines allocate it (16-byte aligned operands, leading dimensions multiples of 4):
+ * wgrad = 0: the forward of N x K over n_scenarios columns; wgrad = 1: the one-period weight gradient of N x K with
+ * nic_wgrad_num_splits(N, K, n_scenarios) splits.  Launches nothing. */
+int nic_linear_models_ok(int32_t N, int32_t K, int32_t n_scenarios, int32_t ldb, int32_t n_models, int32_t wgrad);
+
 /* ---- policy heads (logits -> feasible orders) ------------------------------------------------------------
  * vanilla_warehouse (neural_networks.py:369-427 + apply_softmax_feasibility_function :140-166):
  *   logits Z: [S*Wn + Wn][ldb] (row s*Wn + w = store s from warehouse w; then Wn warehouse rows)

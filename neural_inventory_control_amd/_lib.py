@@ -219,6 +219,10 @@ PROTOTYPES = {
     "nic_linear_bf16_wgrad_periods": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp]),
     "nic_linear_bwd_thin": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "nic_wgrad_reduce": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _vp, _i32, _i32, _f32, _vp]),
+    "nic_linear_fwd_models": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "nic_linear_wgrad_models": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "nic_wgrad_reduce_models": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _f32, _i32, _vp]),
+    "nic_linear_models_ok": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "nic_head_warehouse_fwd": (C.c_int, [_vp, _vp, _vp, _f32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "nic_head_warehouse_bwd": (C.c_int, [_vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
                                          _i32, _vp]),

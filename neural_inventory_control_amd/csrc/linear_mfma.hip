@@ -31,7 +31,9 @@
 // sustained clock (profiles/r01_gemm_pmc_dma256.txt); the remainder is the per-tile DMA wait + barrier (a no-DMA timing
 // build runs 117 TFLOP/s) and the unoverlapped prologue / epilogue of a 1-workgroup-per-CU kernel.
 #include <stdlib.h>
+#include <string.h>
 
+#include "linear_models_plan.h"
 #include "nic_common.h"
 #include "wgrad_plan.h"
 #include "wx_plan.h"
@@ -80,7 +82,21 @@ struct WxParams {
                          // 2 = no B-tile copies, 4 = no barrier per k tile, 32 = s_setprio 1 for waves 4-7 (valid results),
                          // 8 = dgrad without the Hprev prefetch, 16 = stamp 1 behind the plain k tiles, 64 = forward epilogue
                          // straight from the accumulators, 128 = 256 x 256 tiling whatever the shape (8-128: valid results)
+    // model form (MODELS instantiations, grid y = model): floats between two models' A, Bm (0: one shared input), C and bias
+    int64_t mA, mB, mC, mBias;
 };
+
+// Model forms (nic_linear_*_models; csrc/linear_models_plan.h).  A MODELS instantiation advances its operand pointers once, at
+// entry, by blockIdx.y x the model stride (64-bit) and then runs the single-model body unchanged: every offset formed afterwards is
+// an offset inside one model's slice, and grid x is the single-model launch's.  xcd_swizzle(blockIdx.x, gridDim.x) keeps working per
+// model row; as workgroups are dealt over the XCDs in linear order of (y, x), the XCD a logical tile lands on may rotate from model
+// to model when gridDim.x is not a multiple of 8 - a locality matter only (a model's tiles still share their XCD ranges).
+__device__ __forceinline__ void advance_models(WxParams& p) {
+    p.A += nic::linear_model_offset(blockIdx.y, p.mA);
+    p.Bm += nic::linear_model_offset(blockIdx.y, p.mB);
+    p.C += nic::linear_model_offset(blockIdx.y, p.mC);
+    if (p.bias) p.bias += nic::linear_model_offset(blockIdx.y, p.mBias);
+}
 
 // ELU.  libm's expm1f is ~40 VALU instructions and the epilogue applies it to every output element (33.5 M per 512-wide
 // layer at 65,536 scenarios: ~20 us of pure VALU per launch); this branch-free form is a 6-term series near zero (relative
@@ -267,8 +283,9 @@ __device__ __forceinline__ void read_frag8(const float* lds_row, int g, int h, f
 // row-padded (e.g. an unpadded [N][51] weight handed over by HipLinear).  Register-staged double buffering with
 // per-element guards; correctness path, not the performance path (aligned operands use gemm_wx_dma_kernel below).
 // ---------------------------------------------------------------------------------------------------------------
-template <int WAVES_M, int WAVES_N, int MT, int NT, int EPI>
+template <int WAVES_M, int WAVES_N, int MT, int NT, int EPI, bool MODELS = false>
 __global__ __launch_bounds__(kThreads) void gemm_wx_kernel(WxParams p) {
+    if constexpr (MODELS) advance_models(p);
     constexpr int BM = WAVES_M * MT * 32;
     constexpr int BN = WAVES_N * NT * 32;
     static_assert(WAVES_M * WAVES_N == 4, "4 waves per workgroup");
@@ -369,9 +386,10 @@ __global__ __launch_bounds__(kThreads) void gemm_wx_kernel(WxParams p) {
 //   B tile [32][BN] floats, linear (row reads by ds_read_b32 are conflict-free as they are).
 //   Rows past the matrix end are out of range of the buffer descriptor: the DMA writes zeros, no branches.
 // ---------------------------------------------------------------------------------------------------------------
-template <int WAVES_M, int WAVES_N, int MT, int NT, int EPI>
+template <int WAVES_M, int WAVES_N, int MT, int NT, int EPI, bool MODELS = false>
 __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_wx_dma_kernel(WxParams p) {
 #if defined(__HIP_DEVICE_COMPILE__)  // LDS address-space pointers only exist in the device pass
+    if constexpr (MODELS) advance_models(p);
     constexpr int NW = WAVES_M * WAVES_N, NTHREADS = 64 * NW;
     constexpr int BM = WAVES_M * MT * 32;
     constexpr int BN = WAVES_N * NT * 32;
@@ -659,8 +677,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_wx_dma_kernel(WxP
 // only worth it while that stays below ~100 MB - pick_wx_stream (wx_plan.h).
 // Same k order as the LDS-DMA kernel within a group (lanes 0-31: k = kk, lanes 32-63: k = 8 + kk).
 // ---------------------------------------------------------------------------------------------------------------
-template <int NT, int KS, int EPI>
+template <int NT, int KS, int EPI, bool MODELS = false>
 __global__ __launch_bounds__(64 * KS) void gemm_wx_stream_kernel(WxParams p) {
+    if constexpr (MODELS) advance_models(p);
     constexpr int D = 4;
     __shared__ float red[(KS > 1 ? KS - 1 : 1) * NT * 16 * 64];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -786,10 +805,18 @@ struct WgParams {
     // 1,024, an 8-GPU shard of 8,192) then still gives every CU a workgroup.  scen_splits = 0: one group (all slots are
     // scenario splits).
     int scen_splits, periods_per_group;
+    // model form (MODELS instantiations, grid y = model): floats between two models' dY, X and slab
+    int64_t m_dy, m_x, m_slab;
 };
+__device__ __forceinline__ void advance_models(WgParams& p) {
+    p.dY += nic::linear_model_offset(blockIdx.y, p.m_dy);
+    p.X += nic::linear_model_offset(blockIdx.y, p.m_x);
+    p.slab += nic::linear_model_offset(blockIdx.y, p.m_slab);
+}
 
-template <int WAVES_M, int WAVES_N, int MT, int NT, int FAST>
+template <int WAVES_M, int WAVES_N, int MT, int NT, int FAST, bool MODELS = false>
 __global__ __launch_bounds__(kThreads) void gemm_wgrad_kernel(WgParams p) {
+    if constexpr (MODELS) advance_models(p);
     constexpr int BM = WAVES_M * MT * 32;
     constexpr int BN = WAVES_N * NT * 32;
     constexpr int STAGE = (BM + BN) * LDA_S;
@@ -1162,8 +1189,9 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_wgrad_dma_kernel(
 // read exactly once (8 KiB per 16 MFMAs).  slab split index = global wave id; bias column from the dY fragment sums.
 // ---------------------------------------------------------------------------------------------------------------
 // KC = 32-column chunks of the output (K <= 32 KC input features of X): one accumulator and one wave-private B tile each
-template <int KC>
+template <int KC, bool MODELS = false>
 __global__ __launch_bounds__(kThreads) void wgrad_small_kernel(WgParams p, int n_splits) {
+    if constexpr (MODELS) advance_models(p);
     __shared__ __attribute__((aligned(16))) float lds[4 * (1 + KC) * 32 * LDA_S];  // per wave: A tile then KC B tiles, [32][36]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 31, h = lane >> 5;
@@ -1263,8 +1291,17 @@ __global__ __launch_bounds__(kThreads) void wgrad_small_kernel(WgParams p, int n
     if (h == 0 && li < p.N) slab[(int64_t)li * p.lds_ + p.K] += s;
 }
 
+// floats between two models' slab, dW and db (the MODELS instantiations of the two reduce kernels, grid y = model)
+struct ReduceModels { int64_t slab, dW, db; };
+
+template <bool MODELS = false>
 __global__ void wgrad_reduce_kernel(const float* __restrict__ slab, int64_t lds_, int n_splits, float* __restrict__ dW,
-                                    int64_t lddw, float* __restrict__ db, int N, int K, float scale) {
+                                    int64_t lddw, float* __restrict__ db, int N, int K, float scale, ReduceModels m) {
+    if constexpr (MODELS) {
+        slab += nic::linear_model_offset(blockIdx.y, m.slab);
+        dW += nic::linear_model_offset(blockIdx.y, m.dW);
+        if (db) db += nic::linear_model_offset(blockIdx.y, m.db);
+    }
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t total = (int64_t)N * (K + 1);
     if (idx >= total) return;
@@ -1274,6 +1311,30 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ slab, int64_t lds_
     s *= scale;
     if (k < K) dW[(int64_t)n * lddw + k] = s;
     else if (db) db[n] = s;
+}
+
+// many splits, few outputs (the small layers): one wavefront per output element, lanes stride over the splits
+template <bool MODELS = false>
+__global__ void wgrad_reduce_wide_kernel(const float* __restrict__ slab, int64_t lds_, int n_splits, float* __restrict__ dW,
+                                         int64_t lddw, float* __restrict__ db, int N, int K, float scale, ReduceModels m) {
+    if constexpr (MODELS) {
+        slab += nic::linear_model_offset(blockIdx.y, m.slab);
+        dW += nic::linear_model_offset(blockIdx.y, m.dW);
+        if (db) db += nic::linear_model_offset(blockIdx.y, m.db);
+    }
+    const int64_t idx = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (idx >= (int64_t)N * (K + 1)) return;
+    const int n = (int)(idx / (K + 1)), k = (int)(idx % (K + 1));
+    float s = 0.f;
+    for (int sp = lane; sp < n_splits; sp += 64) s += slab[((int64_t)sp * N + n) * lds_ + k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) {
+        s *= scale;
+        if (k < K) dW[(int64_t)n * lddw + k] = s;
+        else if (db) db[n] = s;
+    }
 }
 
 // ---- forward / input gradient: launches.  WHICH kernel runs, over which grid, is decided in wx_plan.h ---------------------------
@@ -1497,36 +1558,139 @@ int nic_linear_wgrad_periods(const float* dY, const float* X, float* slab, int64
                      period_stride_x, stream, who);
 }
 
-// many splits, few outputs (the small layers): one wavefront per output element, lanes stride over the splits
-__global__ void wgrad_reduce_wide_kernel(const float* __restrict__ slab, int64_t lds_, int n_splits, float* __restrict__ dW,
-                                         int64_t lddw, float* __restrict__ db, int N, int K, float scale) {
-    const int64_t idx = (int64_t)blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (idx >= (int64_t)N * (K + 1)) return;
-    const int n = (int)(idx / (K + 1)), k = (int)(idx % (K + 1));
-    float s = 0.f;
-    for (int sp = lane; sp < n_splits; sp += 64) s += slab[((int64_t)sp * N + n) * lds_ + k];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-    if (lane == 0) {
-        s *= scale;
-        if (k < K) dW[(int64_t)n * lddw + k] = s;
-        else if (db) db[n] = s;
-    }
-}
-
 int nic_wgrad_reduce(const float* slab, int64_t lds_, int32_t n_splits, float* dW, int64_t lddw, float* db, int32_t N,
                      int32_t K, float scale, void* stream) {
     NIC_REQUIRE(slab && dW, "nic_wgrad_reduce: null buffer");
     NIC_REQUIRE(N > 0 && K > 0 && lds_ >= K + 1 && lddw >= K && n_splits >= 1, "nic_wgrad_reduce: bad sizes");
     const int64_t total = (int64_t)N * (K + 1);
-    nic::note_kernel(n_splits >= 128 && total <= 65536 ? "wgrad_reduce_wide_kernel" : "wgrad_reduce_kernel");
-    if (n_splits >= 128 && total <= 65536)
-        hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3(nic::ceil_div(total, 4)), dim3(256), 0, nic::as_stream(stream), slab,
-                           lds_, n_splits, dW, lddw, db, N, K, scale);
+    const bool wide = nic::wgrad_reduce_wide(n_splits, N, K);
+    nic::note_kernel(wide ? "wgrad_reduce_wide_kernel" : "wgrad_reduce_kernel");
+    if (wide)
+        hipLaunchKernelGGL(wgrad_reduce_wide_kernel<false>, dim3(nic::ceil_div(total, 4)), dim3(256), 0, nic::as_stream(stream), slab,
+                           lds_, n_splits, dW, lddw, db, N, K, scale, ReduceModels{});
     else
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nic::ceil_div(total, 256)), dim3(256), 0, nic::as_stream(stream), slab, lds_,
-                           n_splits, dW, lddw, db, N, K, scale);
+        hipLaunchKernelGGL(wgrad_reduce_kernel<false>, dim3(nic::ceil_div(total, 256)), dim3(256), 0, nic::as_stream(stream), slab, lds_,
+                           n_splits, dW, lddw, db, N, K, scale, ReduceModels{});
     return nic::check_launch("nic_wgrad_reduce");
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- model forms: the MODELS instantiation of the same kernel over dim3(the single-model grid, n_models) --------------------------
+// (defined HERE, behind the single-model entry points: the tables below are the first use of the model kernels, so they are emitted
+// behind the single-model ones, whose order in the code object stays what it was)
+template <int WM, int WN, int MT, int NT, int EPI = EPI_BIAS_ACT>
+void launch_wx_dma_models(const WxParams& p, int grid, int n_models, hipStream_t s) {
+    hipLaunchKernelGGL((gemm_wx_dma_kernel<WM, WN, MT, NT, EPI, true>), dim3(grid, n_models), dim3(64 * WM * WN), wx_lds_pad(), s, p);
+}
+template <int WM, int WN, int MT, int NT, int EPI = EPI_BIAS_ACT>
+void launch_wx_models(const WxParams& p, int grid, int n_models, hipStream_t s) {
+    hipLaunchKernelGGL((gemm_wx_kernel<WM, WN, MT, NT, EPI, true>), dim3(grid, n_models), dim3(kThreads), 0, s, p);
+}
+template <int NT, int KS, int EPI = EPI_BIAS_ACT>
+void launch_wx_stream_models(const WxParams& p, int grid, int n_models, hipStream_t s) {
+    hipLaunchKernelGGL((gemm_wx_stream_kernel<NT, KS, EPI, true>), dim3(grid, n_models), dim3(64 * KS), 0, s, p);
+}
+// in nic::WxKernel's order, with kWxLaunch's template arguments; null: no model form (nic::lm_wx_has_model_form refuses the request)
+// (forwards only: nothing asks for a model form of the input gradient)
+void (*const kWxLaunchModels[nic::WX_PRODUCT_END])(const WxParams&, int grid, int n_models, hipStream_t) = {
+    launch_wx_stream_models<1, 2>, launch_wx_stream_models<1, 4>,
+    nullptr, launch_wx_dma_models<2, 4, 1, 1>, launch_wx_dma_models<1, 4, 1, 1>,
+    nullptr, launch_wx_models<1, 4, 2, 1>, launch_wx_models<1, 4, 1, 2>,
+};
+
+template <int WM, int WN, int MT, int NT>
+void launch_wg_models(const WgParams& p, int n_splits, bool fast, int n_models, hipStream_t s) {
+    constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
+    dim3 grid(((p.K + 1 + BN - 1) / BN) * ((p.N + BM - 1) / BM) * n_splits, n_models);
+    nic::note_kernelf("gemm_wgrad_kernel<%d,%d,%d,%d,%d,models=%d>", WM, WN, MT, NT, fast ? 1 : 0, n_models);
+    if (fast) hipLaunchKernelGGL((gemm_wgrad_kernel<WM, WN, MT, NT, 1, true>), grid, dim3(kThreads), 0, s, p);
+    else hipLaunchKernelGGL((gemm_wgrad_kernel<WM, WN, MT, NT, 0, true>), grid, dim3(kThreads), 0, s, p);
+}
+template <int KC>
+void launch_wg_small_models(const WgParams& p, int n_splits, bool, int n_models, hipStream_t s) {
+    nic::note_kernelf("wgrad_small_kernel<%d,models=%d>", KC, n_models);
+    hipLaunchKernelGGL((wgrad_small_kernel<KC, true>), dim3((n_splits + 3) / 4, n_models), dim3(kThreads), 0, s, p, n_splits);
+}
+// in nic::WgradTile's order, with kWgLaunch's template arguments; null: the LDS-DMA tiles (nic::lm_wgrad_has_model_form)
+void (*const kWgLaunchModels[nic::WG_STAGED_32x256 + 1])(const WgParams&, int n_splits, bool fast, int n_models, hipStream_t) = {
+    launch_wg_small_models<1>, launch_wg_small_models<2>, launch_wg_small_models<3>, launch_wg_small_models<4>,
+    nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+    launch_wg_models<2, 2, 2, 2>, launch_wg_models<2, 2, 2, 1>, launch_wg_models<1, 4, 2, 1>, launch_wg_models<1, 4, 1, 2>};
+
+}  // namespace
+
+extern "C" {
+
+// ---- K models in one launch (csrc/linear_models_plan.h: checks and plan; grid y = model) ----------------------------------------
+// nic_last_kernel: the single-model kernel's name with ",models=K>" in place of the closing ">"; the two reduce kernels have no
+// template list and get the suffix ",models=K" appended.
+int nic_linear_fwd_models(const float* W, int64_t ldw, int64_t W_stride, const float* bias, int64_t bias_stride, const float* X,
+                          int64_t X_stride, float* Y, int64_t Y_stride, int32_t N, int32_t K, int32_t n_scenarios, int32_t ldb,
+                          int32_t act, int32_t n_models, void* stream) {
+    const nic::LmFwdRequest r{reinterpret_cast<uintptr_t>(W), reinterpret_cast<uintptr_t>(bias), reinterpret_cast<uintptr_t>(X),
+                              reinterpret_cast<uintptr_t>(Y), ldw, W_stride, bias_stride, X_stride, Y_stride, N, K, n_scenarios, ldb,
+                              act, n_models};
+    WxParams p{W, ldw, X, Y, bias, nullptr, N, K, (n_scenarios + 3) / 4 * 4, ldb, act, 0, tune_flags(), W_stride, X_stride, Y_stride,
+               bias_stride};
+    const nic::LmFwdPlan plan = nic::linear_models_fwd_plan(r, nic::cu_count(), wx_force(p));
+    NIC_REQUIRE(plan.refusal == nic::LM_OK, "nic_linear_fwd_models: %s", nic::linear_models_reason(plan.refusal));
+    const char* name = wx_kernel_names<EPI_BIAS_ACT>().name[plan.plan.kernel];
+    nic::note_kernelf("%.*s,models=%d>", (int)strlen(name) - 1, name, n_models);
+    kWxLaunchModels[plan.plan.kernel](p, plan.plan.grid, n_models, nic::as_stream(stream));
+    return nic::check_launch("nic_linear_fwd_models");
+}
+
+int nic_linear_wgrad_models(const float* dY, int64_t dY_stride, const float* X, int64_t X_stride, float* slab, int64_t slab_stride,
+                            int64_t lds_, int32_t N, int32_t K, int32_t n_scenarios, int32_t ldb, int32_t n_splits, int32_t n_models,
+                            void* stream) {
+    const nic::LmWgradRequest r{reinterpret_cast<uintptr_t>(dY), reinterpret_cast<uintptr_t>(X), reinterpret_cast<uintptr_t>(slab),
+                                dY_stride, X_stride, slab_stride, lds_, N, K, n_scenarios, ldb, n_splits, n_models};
+    const nic::LmWgradPlan lm = nic::linear_models_wgrad_plan(r, gemm_variant() == 2);
+    NIC_REQUIRE(lm.refusal == nic::LM_OK, "nic_linear_wgrad_models: %s", nic::linear_models_reason(lm.refusal));
+    const nic::WgradPlan& plan = lm.plan;
+    const nic::WgradLaunch l = nic::wgrad_launch(plan, 1, 0);   // (nic_linear_wgrad's one launch)
+    WgParams p{dY, X, slab, lds_, ldb, N, K, n_scenarios, plan.chunk, gemm_variant() == 3 ? 0 : 1, l.n_periods, 0, 0, plan.flush_periods,
+               plan.scen_splits, plan.periods_per_group, dY_stride, X_stride, slab_stride};
+    kWgLaunchModels[l.tile](p, plan.slots, lm.operands.buffer, n_models, nic::as_stream(stream));
+    return nic::check_launch("nic_linear_wgrad_models");
+}
+
+int nic_wgrad_reduce_models(const float* slab, int64_t slab_stride, int64_t lds_, int32_t n_splits, float* dW, int64_t lddw,
+                            int64_t dW_stride, float* db, int64_t db_stride, int32_t N, int32_t K, float scale, int32_t n_models,
+                            void* stream) {
+    const nic::LmReduceRequest r{reinterpret_cast<uintptr_t>(slab), reinterpret_cast<uintptr_t>(dW), reinterpret_cast<uintptr_t>(db),
+                                 slab_stride, lds_, lddw, dW_stride, db_stride, N, K, n_splits, n_models};
+    const int refusal = nic::linear_models_check_reduce(r);
+    NIC_REQUIRE(refusal == nic::LM_OK, "nic_wgrad_reduce_models: %s", nic::linear_models_reason(refusal));
+    const int64_t total = (int64_t)N * (K + 1);
+    const bool wide = nic::wgrad_reduce_wide(n_splits, N, K);
+    nic::note_kernelf(wide ? "wgrad_reduce_wide_kernel,models=%d" : "wgrad_reduce_kernel,models=%d", n_models);
+    const ReduceModels m{slab_stride, dW_stride, db_stride};
+    if (wide)
+        hipLaunchKernelGGL(wgrad_reduce_wide_kernel<true>, dim3(nic::ceil_div(total, 4), n_models), dim3(256), 0, nic::as_stream(stream),
+                           slab, lds_, n_splits, dW, lddw, db, N, K, scale, m);
+    else
+        hipLaunchKernelGGL(wgrad_reduce_kernel<true>, dim3(nic::ceil_div(total, 256), n_models), dim3(256), 0, nic::as_stream(stream),
+                           slab, lds_, n_splits, dW, lddw, db, N, K, scale, m);
+    return nic::check_launch("nic_wgrad_reduce_models");
+}
+
+// 1 if the model forms take a layer as the engines allocate it (16-byte aligned operands, leading dimensions multiples of 4):
+// wgrad = 0: the forward of N x K over n_scenarios columns; wgrad = 1: the one-period weight gradient of N x K with
+// nic_wgrad_num_splits(N, K, n_scenarios) splits.  Launches nothing; no device access besides the compute-unit count.
+int nic_linear_models_ok(int32_t N, int32_t K, int32_t n_scenarios, int32_t ldb, int32_t n_models, int32_t wgrad) {
+    const int64_t lda = (K + 3) / 4 * 4;
+    if (wgrad) {
+        const int n_splits = nic::wgrad_recommended_slots(N, K, n_scenarios, nic::cu_count());
+        const int64_t lds_ = (K + 1 + 3) / 4 * 4;
+        const nic::LmWgradRequest r{16, 16, 16, (int64_t)N * ldb, (int64_t)K * ldb, (int64_t)(n_splits > 0 ? n_splits : 1) * N * lds_, lds_,
+                                    N, K, n_scenarios, ldb, n_splits, n_models};
+        return nic::linear_models_wgrad_plan(r).refusal == nic::LM_OK;
+    }
+    const nic::LmFwdRequest r{16, 16, 16, 16, lda, (int64_t)N * lda, N, 0, (int64_t)N * ldb, N, K, n_scenarios, ldb, NIC_ACT_NONE, n_models};
+    return nic::linear_models_fwd_plan(r, nic::cu_count()).refusal == nic::LM_OK;
 }
 }

@@ -6,19 +6,29 @@ A whole-horizon launch of the reference's real-data batch (72 products x 21 stor
 workgroups: a serial chain of 95 periods on 2 % of the device.  Seeds, learning rates or initialisations of one architecture ride in
 the idle CUs instead of paying K steps.  Every model runs the instruction stream of the single-model kernels on its own slice of
 the buffers, and the four GEMMs around the launch pair (the observation rows' share of the first layer, three weight gradients)
-are launched per model with the operands, shapes and strides `FusedRollout`'s whole-horizon route uses - so each model's costs,
+run with the operands, shapes, strides and split counts `FusedRollout`'s whole-horizon route uses - so each model's costs,
 final state and gradients are the bits `FusedRollout(model).run` gives for it (trainer.py:181-216 once per model).  The totals are
 one fixed-order reduction for all K models (the cost half of `nic_small_rollout_ensemble_reduce`): they agree with the single-model
 `torch.sum` to rounding, not to the bit.
 
+The GEMMs are one launch each for all K models (`nic_linear_fwd_models`, `nic_linear_wgrad_models`, `nic_wgrad_reduce_models`,
+csrc/linear_models_plan.h: grid y = model, the single-model plan and kernel on every model's slice, so not a bit of any model's
+result changes): one forward, and per layer one `zero_()` of a [K][splits][N][ld] slab, one contraction and one reduction straight
+into the [K][P] gradient rows.  `model_gemms = False` - and any shape `ops.linear_models_ok` refuses - takes the per-model loop of
+single-model calls instead (4 K GEMM launches + 6 K around them).
+
+`run` alone leaves the optimizer to the caller and packs all K models' weights again every call.  The whole training step is
+`train_step`: after `bind_parameters()` every model's `weight` / `bias` are views of its row of `weights [K][P]`, nothing is packed,
+and an `EnsembleAdam(K, P)` updates all K rows with two launches - no per-model Python.  `fit` is the epoch loop over `train_step`
+with the best weights per model kept on the device (ensemble_step.py, shared with `SmallPolicyEnsemble`).
+
 Layout: weights `[K][P]` in `nn.Linear`'s own order (per layer the weight, row-major, then the bias; packed with one `torch.cat`
-per run - an `EnsembleAdam(K, P)` can step such a buffer), gradients `[K][P]` in the same order (`param.grad` are views of it),
+per run unless the parameters are bound), gradients `[K][P]` in the same order (`param.grad` are views of it),
 inputs `X [K][F][T][ldb]` (the kernel writes model m's state rows into X[m]; the observation rows are model-independent, filled once
 and copied), `z1_obs [K][H1][T][ldb]`, costs `rewards [K][T][ldb]`, histories and pre-activation gradients `[K][rows][T][ldb]`.
 
-Not part of this engine: `bind_parameters` / `train_step` / `fit`, graph replay, problem instances per model, Trainer / YAML /
-`main_run` wiring, a `torch.library` operator, multi-GPU sharding.  The optimizer is the caller's (K optimizers, or one with K
-parameter groups, step the models independently).
+Not part of this engine: graph replay, problem instances per model, Trainer / YAML / `main_run` wiring, a `torch.library` operator,
+multi-GPU sharding, bf16 GEMMs.
 """
 import types
 
@@ -27,6 +37,7 @@ import torch
 from . import _lib, ops
 from . import horizon_rollout as hz
 from . import small_rollout as sr
+from .ensemble_step import bind_rows, EnsembleStep, materialized_width
 from .layout import demand_trace_soa, Table
 from .rollout import _pad32, FusedRollout
 from .small_ensemble import pack_ensemble_weights
@@ -79,7 +90,7 @@ def grad_views(grad, dims):
             for m in range(grad.shape[0])]
 
 
-class HorizonPolicyEnsemble:
+class HorizonPolicyEnsemble(EnsembleStep):
     def __init__(self, models, problem_params, device):
         self.models = check_models(models)
         _lib.require_device()
@@ -92,6 +103,11 @@ class HorizonPolicyEnsemble:
         self._key = None
         self.plan = self.prob = None
         self.weights = self.grad = self._grad_views = None   # [K][P], [K][P]
+        self.model_gemms = True         # one GEMM launch for all K models where the library takes the shape; False: the per-model loop
+        self.param_shapes = None        # shapes of one model's parameters in `parameters()` order (EnsembleAdam's `param_shapes`)
+        self._bind_requested = self._bound = False
+        self._dims_bound = None         # layer sizes, once the parameters are bound
+        self.best_dev = self.best_weights = None   # `fit`: [K] lowest dev loss so far, [K][P] the parameters that gave it
 
     @property
     def n_models(self):
@@ -107,6 +123,31 @@ class HorizonPolicyEnsemble:
                 raise ValueError(f"model {i}: layer sizes {d} differ from model 0's {dims[0]}")
         return lins, dims[0]
 
+    def _model_buffers(self, dims):
+        P = packed_count(dims)
+        if self.weights is None or self.weights.shape[1] != P:
+            if self._bound:
+                raise ValueError(f"HorizonPolicyEnsemble: layer sizes {list(dims)} differ from the bound parameters'")
+            self.weights, self.grad, self._grad_views = torch.zeros(self.n_models, P, device=self.device), None, None
+            self.param_shapes = [shape for _, n, k, _ in layer_slices(dims) for shape in ((n, k), (n,))]
+
+    def _bind(self, lins, dims):
+        """weight.data / bias.data of every layer <- views of the model's row of `weights`, which gets the current values once"""
+        pack_ensemble_weights(lins, self.weights)
+        bind_rows(lins, self.weights, layer_slices(dims))
+        self._bound, self._dims_bound = True, list(dims)
+
+    def bind_parameters(self):
+        """Opt-in: from now on the models' parameters LIVE in `weights [K][P]` (views of their rows), `run` and `train_step` pack
+        nothing, and whatever writes a parameter in place - `load_state_dict`, an optimizer - writes the packed row.  Binds now if
+        the input width is known (a materialised first layer), else on the first batch."""
+        self._bind_requested = True
+        F = materialized_width(self.models)
+        if F is not None and not self._bound:
+            lins, dims = self._dims(F)
+            self._model_buffers(dims)
+            self._bind(lins, dims)
+
     def _setup(self, prob, T, train, dims, shift):
         K, dev, ld = self.n_models, self.device, prob.ldb
         key = (prob.B, T, K, tuple(dims), prob.S, prob.Wn, prob.Ws, prob.Ww, shift)
@@ -120,9 +161,7 @@ class HorizonPolicyEnsemble:
                                  f"{FD} state rows, {prob.B} scenarios x {T} periods)")
             self.plan = hz.HorizonPlan(prob, dims)
             z = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
-            P = packed_count(dims)
-            if self.weights is None or self.weights.shape[1] != P:
-                self.weights, self.grad, self._grad_views = z(K, P), None, None
+            self._model_buffers(dims)
             self.F, self.F_dyn, self.dims = F, FD, list(dims)
             self.state0 = z(FD, ld)
             self.rewards, self.final = z(K, T, ld), z(K, FD, ld)
@@ -140,6 +179,11 @@ class HorizonPolicyEnsemble:
             self._reduce = sr.ensemble_strides(K, rewards=T * ld, scratch=n_scratch)
             self._strides = None
             self._checked = False
+            # once per shape: do the model-batched GEMMs take it (the first layer's observation share, three one-period weight
+            # gradients over T * ld columns)?  If not, `run` takes the per-model loop.
+            n_cols = T * ld
+            self._models_ok = (ops.linear_models_ok(dims[1], F - FD, n_cols, n_cols, K)
+                               and all(ops.linear_models_ok(dims[i + 1], dims[i], n_cols, n_cols, K, wgrad=True) for i in range(3)))
             self._key = key
         if train and self.hist is None:
             # the training buffers come with the first training run of a shape and stay: evaluation runs in between use the rest
@@ -149,9 +193,9 @@ class HorizonPolicyEnsemble:
             self.hist = [z(K, r, T, ld) for r in rows]
             self.dz = [z(K, dims[i + 1], T, ld) for i in range(3)]   # (padding columns stay zero: the kernel writes live ones only)
             self.g_reward, self._g_reward_key = z(ld), None
-            # (one set of slabs: the K weight-gradient contractions of a layer follow each other on the stream)
+            # (a slab per model: one launch contracts a layer for all K; the per-model loop uses model 0's, one contraction after the other)
             self.splits = [ops.wgrad_num_splits(dims[i + 1], dims[i], n_cols) for i in range(3)]
-            self.slabs = [z(self.splits[i], dims[i + 1], (dims[i] + 1 + 3) // 4 * 4) for i in range(3)]
+            self.slabs = [z(K, self.splits[i], dims[i + 1], (dims[i] + 1 + 3) // 4 * 4) for i in range(3)]
             if self.grad is None:
                 self.grad = z(K, self.weights.shape[1])
                 self._grad_views = grad_views(self.grad, dims)
@@ -193,6 +237,21 @@ class HorizonPolicyEnsemble:
         whole-horizon kernels do not take is a ValueError: there is no fall-back to K single steps."""
         if discrete_allocation and train:
             raise ValueError("discrete_allocation is an evaluation-time option of the fused rollout")
+        tt = self._step(data, periods, ignore_periods, train, observation_params, grad_scale, discrete_allocation, None)
+        if train:
+            sr.assign_grads(self.param_grads(), accumulate_grads)
+        return tt[:, 0], tt[:, 1]
+
+    def train_step(self, data, periods, ignore_periods=0, optimizer=None, observation_params=None, grad_scale=None):
+        """One whole training step of all K models: forward, the cost reduction, backward, the batched weight gradients and
+        `optimizer.step(self.weights, self.grad)` (an `EnsembleAdam` over this engine's (K, P)) - no packing, no `param.grad`, no
+        per-model Python.  Needs `bind_parameters()`.  Returns (total [K], reported [K]) of the step BEFORE the update, as `run`
+        does."""
+        self._require_step(optimizer)
+        tt = self._step(data, periods, ignore_periods, True, observation_params, grad_scale, False, optimizer)
+        return tt[:, 0], tt[:, 1]
+
+    def _step(self, data, periods, ignore_periods, train, observation_params, grad_scale, discrete_allocation, optimizer):
         lead, dev, K = self._engines[0], self.device, self.n_models
         if not FusedRollout.observation_ok(self.models[0], observation_params, data):
             raise ValueError("data_driven needs a past-demand window and the days_from_christmas time feature")
@@ -202,7 +261,12 @@ class HorizonPolicyEnsemble:
         P_ = observation_params["demand"]["past_periods"]
         FD = prob.S * prob.Ws + prob.Wn * prob.Ww
         F = FD + prob.S * P_ + 2 * prob.S + data["days_from_christmas"].shape[1] + prob.S * data["lead_times"].shape[2]
-        lins, dims = self._dims(F)
+        if self._bound:   # (nothing is packed, and the per-model checks were made when the parameters were bound)
+            lins, dims = None, self._dims_bound
+            if dims[0] != F:
+                raise ValueError(f"HorizonPolicyEnsemble: this batch gives the policy {F} input rows, the bound parameters have {dims[0]}")
+        else:
+            lins, dims = self._dims(F)
         if prob.E != 0 or len(dims) != 4:
             raise ValueError(f"HorizonPolicyEnsemble: the whole-horizon kernels do not take this setting / policy (layer sizes {dims}, "
                              f"{prob.E} extra echelons)")
@@ -210,8 +274,15 @@ class HorizonPolicyEnsemble:
         if demand_soa.shape[0] < T + shift:
             raise ValueError("Current period is greater than the number of periods in the data")
         self._setup(prob, T, train, dims, shift)
+        if optimizer is not None:
+            self._require_optimizer_shape(optimizer)
         Fo, n_cols = F - FD, T * ld
-        pack_ensemble_weights(lins, self.weights)   # (every run: the optimizers moved the parameters)
+        if self._bind_requested and not self._bound:
+            self._bind(lins, dims)
+        if not self._bound:
+            pack_ensemble_weights(lins, self.weights)   # (every run: the optimizers moved the parameters)
+        batched = self.model_gemms and self._models_ok
+        P, sl = self.weights.shape[1], layer_slices(dims)
         a = prob.S * prob.Ws
         self.state0[:a].view(prob.S, prob.Ws, ld)[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
         if prob.Wn:
@@ -222,14 +293,22 @@ class HorizonPolicyEnsemble:
         lead._fill_observation_rows(X[0].transpose(0, 1), data, prob, T, shift, observation_params, demand_soa)
         if K > 1:
             X[1:, FD:].copy_(X[0, FD:].unsqueeze(0).expand(K - 1, Fo, T, ld))
-        # per model, with the single-model route's operands: the observation rows' share of the first layer for every period (+ bias)
-        for m, ls in enumerate(lins):
-            self.W1obs[m, :, :Fo].copy_(ls[0].weight.detach()[:, FD:])
-            ops.linear_fwd(self.W1obs[m, :, :Fo], ls[0].bias.detach(), X[m, FD:].view(Fo, n_cols), self.z1[m].view(dims[1], n_cols), n_cols,
-                           _lib.NIC_ACT_NONE)
-        # the descriptor points at model 0's row of the packed weights
+        # with the single-model route's operands: the observation rows' share of the first layer for every period (+ bias)
         row0 = self.weights[0]
-        views = [types.SimpleNamespace(weight=row0[o:o + n * k].view(n, k), bias=row0[bo:bo + n]) for o, n, k, bo in layer_slices(dims)]
+        if batched:
+            # one strided copy and one launch: the weights and biases are read in the packed rows, the observation rows are shared
+            o, n, k, bo = sl[0]
+            self.W1obs[:, :, :Fo].copy_(self.weights[:, o:o + n * k].view(K, n, k)[:, :, FD:])
+            ops.linear_fwd_models(self.W1obs[:, :, :Fo], row0[bo:bo + n], X[0, FD:].view(Fo, n_cols), self.z1.view(K, dims[1], n_cols),
+                                  n_cols, _lib.NIC_ACT_NONE, bias_stride=P)
+        else:
+            for m, ls in enumerate(lins or [eng._linears() for eng in self._engines]):
+                self.W1obs[m, :, :Fo].copy_(ls[0].weight.detach()[:, FD:])
+                ops.linear_fwd(self.W1obs[m, :, :Fo], ls[0].bias.detach(), X[m, FD:].view(Fo, n_cols), self.z1[m].view(dims[1], n_cols),
+                               n_cols, _lib.NIC_ACT_NONE)
+        self._note("z1")
+        # the descriptor points at model 0's row of the packed weights
+        views = [types.SimpleNamespace(weight=row0[o:o + n * k].view(n, k), bias=row0[bo:bo + n]) for o, n, k, bo in sl]
         desc = self.plan.desc(prob, T, shift, views, self.edge_mask, demand_soa, n_cols, round_orders=discrete_allocation)
         if not self._checked:   # once per shape: the library's own limits
             if not hz.horizon_ok(desc):
@@ -245,21 +324,37 @@ class HorizonPolicyEnsemble:
                                          self.scratch)
         tt = self.totals.clone()   # (the caller's tensors must not change under a later run)
         if not train:
-            return tt[:, 0], tt[:, 1]
+            return tt
         if grad_scale is None:
             grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
         self._g_reward_key = sr.set_g_reward(self.g_reward, B, grad_scale, self._g_reward_key)
         hz.horizon_ensemble_bwd(desc, ens, *hist, Table(self.g_reward, 0, 1), *self.dz)
         self._note("bwd")
         # three weight gradients per model: FusedRollout._wgrad_over_columns' launches on model m's slices
-        for m, (gw, gb) in enumerate(self._grad_views):
-            inputs = [X[m], self.hist[0][m], self.hist[1][m]]
-            for i, x in enumerate(inputs):
+        if batched:
+            for i, x in enumerate((X, self.hist[0], self.hist[1])):   # per layer, all K models: zero, contract, reduce into grad[:, ...]
+                o, n, k, bo = sl[i]
                 self.slabs[i].zero_()
-                ops.linear_wgrad(self.dz[i][m].flatten(1), x.flatten(1), self.slabs[i], n_cols)
-                ops.wgrad_reduce(self.slabs[i], gw[i], gb[i], dims[i], 1.0)
-        sr.assign_grads(self.param_grads(), accumulate_grads)
-        return tt[:, 0], tt[:, 1]
+                ops.linear_wgrad_models(self.dz[i].flatten(2), x.flatten(2), self.slabs[i], n_cols)
+                self._note("wgrad%d" % i)
+                ops.wgrad_reduce_models(self.slabs[i], self.grad[0, o:o + n * k].view(n, k), self.grad[0, bo:bo + n], k, 1.0,
+                                        dW_stride=P, db_stride=P)
+                self._note("reduce%d" % i)
+        else:
+            for m, (gw, gb) in enumerate(self._grad_views):
+                inputs = [X[m], self.hist[0][m], self.hist[1][m]]
+                for i, x in enumerate(inputs):
+                    slab = self.slabs[i][0]
+                    slab.zero_()
+                    ops.linear_wgrad(self.dz[i][m].flatten(1), x.flatten(1), slab, n_cols)
+                    if m == 0:   # (the K models of a layer run the same kernel: noted once)
+                        self._note("wgrad%d" % i)
+                    ops.wgrad_reduce(slab, gw[i], gb[i], dims[i], 1.0)
+                    if m == 0:
+                        self._note("reduce%d" % i)
+        if optimizer is not None:
+            optimizer.step(self.weights, self.grad)
+        return tt
 
     # ---- inspection helpers used by the parity tests --------------------------------------------------------------------------------
     def per_period_rewards(self):

@@ -31,7 +31,7 @@ import torch
 
 from . import _lib
 from . import small_rollout as sr
-from .ensemble_adam import EnsembleAdam
+from .ensemble_step import bind_rows, EnsembleStep, materialized_width
 from .launch_replay import LaunchReplay, ReplayedEngine
 from .layout import demand_trace_soa, EnvProblem, Table
 from .rollout import _HEADS, FusedRollout
@@ -158,7 +158,7 @@ class _ShapeState:
 _MAX_KEPT_SHAPES = 4   # other batch shapes kept while their launches are replayed (an epoch has up to four: full / short x train / dev)
 
 
-class SmallPolicyEnsemble(ReplayedEngine):
+class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
     def __init__(self, models, problem_params, device):
         self.models = check_models(models)
         _lib.require_device()
@@ -215,11 +215,7 @@ class SmallPolicyEnsemble(ReplayedEngine):
     def _bind(self, lins, dims):
         """weight.data / bias.data of every layer <- views of the model's row of `weights`, which gets the current values once"""
         pack_ensemble_weights(lins, self.weights)
-        for m, ls in enumerate(lins):
-            row = self.weights[m]
-            for lin, (o, n, k, bo) in zip(ls, sr.layer_slices(dims[0], len(dims) - 2, dims[-1])):
-                lin.weight.data = row[o:o + n * k].view(n, k)
-                lin.bias.data = row[bo:bo + n]
+        bind_rows(lins, self.weights, sr.layer_slices(dims[0], len(dims) - 2, dims[-1]))
         self._bound, self._dims_bound = True, dims
 
     def bind_parameters(self):
@@ -227,10 +223,9 @@ class SmallPolicyEnsemble(ReplayedEngine):
         nothing, and whatever writes a parameter in place - `load_state_dict`, an optimizer - writes the packed row.  Binds now if
         the input width is known (a materialised first layer), else on the first batch."""
         self._bind_requested = True
-        known = [ls[0].in_features for ls in (m.master_linears() for m in self.models)
-                 if not isinstance(ls[0].weight, torch.nn.parameter.UninitializedParameter)]
-        if known and not self._bound:
-            lins = self._materialized(known[0])
+        known = materialized_width(self.models)
+        if known is not None and not self._bound:
+            lins = self._materialized(known)
             dims = self._dims(lins)
             self._model_buffers(dims)
             self._bind(lins, dims)
@@ -342,10 +337,7 @@ class SmallPolicyEnsemble(ReplayedEngine):
         backward, the reduction's two launches and `optimizer`'s two (an
         `EnsembleAdam` over this engine's (K, P)) - no packing, no `param.grad`, no per-model Python.  Needs `bind_parameters()`.
         Returns (total [K], reported [K]) of the step BEFORE the update, as `run` does."""
-        if not self._bind_requested:
-            raise ValueError("SmallPolicyEnsemble.train_step needs bound parameters: call bind_parameters() first")
-        if not isinstance(optimizer, EnsembleAdam):
-            raise ValueError("SmallPolicyEnsemble.train_step needs an EnsembleAdam as `optimizer`")
+        self._require_step(optimizer)
         tt = self._step(data, periods, ignore_periods, True, observation_params, demand_soa, grad_scale, False, optimizer)
         return tt[:, 0], tt[:, 1]
 
@@ -374,9 +366,8 @@ class SmallPolicyEnsemble(ReplayedEngine):
         if demand_soa.shape[0] < T + shift:
             raise ValueError("Current period is greater than the number of periods in the data")
         lins = self._setup(prob, T, train)
-        if optimizer is not None and (optimizer.n_models, optimizer.P) != tuple(self.weights.shape):
-            raise ValueError(f"SmallPolicyEnsemble.train_step: the optimizer is for {optimizer.n_models} models of {optimizer.P} parameters, "
-                             f"the engine has {K} of {self.weights.shape[1]}")
+        if optimizer is not None:
+            self._require_optimizer_shape(optimizer)
         sh = self._shape
         replay = sh.replay
         # a captured sequence holds raw pointers: it reads the pinned problem's tables and the staged demand trace, refreshed in place
@@ -447,9 +438,8 @@ class SmallPolicyEnsemble(ReplayedEngine):
                              f"got {tuple(demand_soa.shape)}")
         layouts = tuple((name, getattr(prob0, name).scn_stride) for name in EnvProblem._TABLES if getattr(prob0, name).tensor is not None)
         lins = self._setup(prob0, T, train, instances=("instances", I, T_total, layouts))
-        if optimizer is not None and (optimizer.n_models, optimizer.P) != tuple(self.weights.shape):
-            raise ValueError(f"SmallPolicyEnsemble.train_step: the optimizer is for {optimizer.n_models} models of {optimizer.P} parameters, "
-                             f"the engine has {K} of {self.weights.shape[1]}")
+        if optimizer is not None:
+            self._require_optimizer_shape(optimizer)
         sh = self._shape
         replay = sh.replay
         F = sh.plan.F
@@ -512,40 +502,3 @@ class SmallPolicyEnsemble(ReplayedEngine):
         replay.probe_end()
         replay.ran()
         return sh.totals.clone()
-
-    # ---- epochs ------------------------------------------------------------------------------------------------------------------
-    def fit(self, train_batches, dev_batches, epochs, periods, dev_periods, ignore_periods, optimizer, observation_params=None):
-        """`epochs` times: `train_step` over `train_batches`, then `run(train=False)` over `dev_batches` (each batch a dict, or a list
-        of I instances' dicts; the sample count is per instance).  Returns the train and dev
-        histories [epochs][K]: the reported cost per (scenario, reported period, store) as `Trainer.do_one_epoch` averages it.
-        The best dev loss per model and the parameters that gave it are tracked on the device (`best_dev [K]`, `best_weights
-        [K][P]`, updated with a mask): no host synchronisation inside an epoch.  `load_best()` puts them back."""
-        K, dev = self.n_models, self.device
-        hist = [torch.zeros(epochs, K, device=dev), torch.zeros(epochs, K, device=dev)]
-        n_stores = self.problem_params["n_stores"]
-        for epoch in range(epochs):
-            for which, batches, T in ((0, train_batches, periods), (1, dev_batches, dev_periods)):
-                samples = 0
-                for data in batches:
-                    if which == 0:
-                        _, reported = self.train_step(data, T, ignore_periods, optimizer, observation_params)
-                    else:
-                        _, reported = self.run(data, T, ignore_periods, train=False, observation_params=observation_params)
-                    hist[which][epoch] += reported
-                    samples += (data[0] if isinstance(data, (list, tuple)) else data)["demands"].shape[0]   # (per instance)
-                if samples == 0:
-                    raise ValueError("SmallPolicyEnsemble.fit needs at least one training batch and one dev batch")
-                hist[which][epoch] /= float(samples * (T - ignore_periods) * n_stores)
-            if self.best_dev is None:
-                self.best_dev = torch.full((K,), float("inf"), device=dev)
-                self.best_weights = self.weights.clone()
-            better = hist[1][epoch] < self.best_dev
-            self.best_dev = torch.where(better, hist[1][epoch], self.best_dev)
-            self.best_weights = torch.where(better[:, None], self.weights, self.best_weights)
-        return hist[0], hist[1]
-
-    def load_best(self):
-        """bound parameters <- `best_weights` (the parameters after the epoch with each model's lowest dev loss)"""
-        if self.best_weights is None or not self._bound:
-            raise ValueError("SmallPolicyEnsemble.load_best: no fit() has run on bound parameters")
-        self.weights.copy_(self.best_weights)
