@@ -1,20 +1,51 @@
-"""What the K-model engines (`SmallPolicyEnsemble`, `HorizonPolicyEnsemble`) share around their `train_step`: binding the models'
-parameters to the rows of `weights [K][P]`, the optimizer check, and the epoch loop `fit` / `load_best` with the best weights per
-model kept on the device.  An engine provides `n_models`, `device`, `problem_params`, `weights`, `_bind_requested`, `_bound`,
-`best_dev`, `best_weights`, `train_step` and `run`."""
+"""What the K-model engines (`SmallPolicyEnsemble`, `HorizonPolicyEnsemble`) share around their kernels.
+
+The packed-row layout: `weights [K][P]`, row m = model m's layers in `nn.Linear`'s own order (per layer the weight, row-major, then
+the bias) - `layer_slices`, `packed_count`, `grad_views`, `pack_ensemble_weights`, all on `dims = [F, H1, ..., n_out]`.
+
+`EnsembleStep`, the engines' base: the borrowed single-model engines (problem cache and LazyLinear materialisation are theirs),
+materialising and comparing the models' layers, `weights` and binding the models' parameters to its rows, what a step does with the
+weights before it launches (bound: nothing; bind requested: bind on the first batch; else pack, every run), the frames of `run` and
+`train_step` around an engine's `_step`, and the epoch loop `fit` / `load_best` with the best weights per model kept on the device.
+An engine provides `_step`, `run` and `train_step` with its own signatures, and sizes `grad` / `_grad_views` with its buffers.
+`check_model_list` is the part of the engines' `check_models` that does not depend on the policy."""
 import torch
 
+from . import _lib
+from . import small_rollout as sr
 from .ensemble_adam import EnsembleAdam
+from .rollout import FusedRollout
+
+MAX_MODELS = 65535   # (grid y = model)
 
 
-def bind_rows(linears_per_model, weights, slices):
-    """weight.data / bias.data of every layer <- views of the model's row of `weights`; slices: [(weight offset, rows, cols, bias
-    offset)] per layer.  The rows must already hold the current values."""
-    for m, ls in enumerate(linears_per_model):
-        row = weights[m]
-        for lin, (o, n, k, bo) in zip(ls, slices):
-            lin.weight.data = row[o:o + n * k].view(n, k)
-            lin.bias.data = row[bo:bo + n]
+def layer_slices(dims):
+    """[(weight offset, rows, cols, bias offset)] per layer of one model's packed row; dims = [F, H1, ..., n_out]"""
+    out, off = [], 0
+    for k, n in zip(dims[:-1], dims[1:]):
+        out.append((off, n, k, off + n * k))
+        off += n * k + n
+    return out
+
+
+def packed_count(dims):
+    return sum(n * k + n for k, n in zip(dims[:-1], dims[1:]))
+
+
+def grad_views(grad, dims):
+    """[(weight gradients per layer, bias gradients per layer)] per model: views into grad [K][>= P] in the packed-weight layout"""
+    sl = layer_slices(dims)
+    return [([grad[m, o:o + n * k].view(n, k) for o, n, k, _ in sl], [grad[m, bo:bo + n] for _, n, _, bo in sl])
+            for m in range(grad.shape[0])]
+
+
+def pack_ensemble_weights(linears_per_model, out=None):
+    """[K][P]: row m = `pack_weights` of model m's layers, all K models in ONE torch.cat (one launch)."""
+    K = len(linears_per_model)
+    flat = sr.pack_weights([lin for lins in linears_per_model for lin in lins], None if out is None else out.view(-1))
+    if flat.numel() % K != 0:
+        raise ValueError("pack_ensemble_weights: the models do not have the same number of parameters")
+    return flat.view(K, -1) if out is None else out
 
 
 def materialized_width(models):
@@ -24,7 +55,138 @@ def materialized_width(models):
     return known[0] if known else None
 
 
+def check_model_list(models, who, policies, handles, arch, mismatch, own=None, versus_first=None):
+    """What engine `who` asks of its models whatever the policy: 1..65,535 of them, each a policy named in `policies` that
+    `FusedRollout` takes (else "`who` handles `handles`"), with a bias in every layer and `arch(model)` equal to model 0's
+    (`mismatch`: the message's format for the two).  The engine's own rules keep their places: `own(i, model)`, on one model,
+    follows the policy check; `versus_first(i, model, first)` follows the architecture's.  ValueError names the first mismatch.
+    Host-side only."""
+    models = list(models)
+    if len(models) < 1:
+        raise ValueError(f"{who} needs at least one model")
+    if len(models) > MAX_MODELS:
+        raise ValueError(f"{who} takes at most 65,535 models")
+    for i, m in enumerate(models):
+        name = getattr(m, "nn_args", {}).get("name") if hasattr(m, "nn_args") else None
+        if name not in policies or not FusedRollout.supports(m):
+            raise ValueError(f"model {i}: {who} handles {handles}, got {name!r}")
+        if own is not None:
+            own(i, m)
+        if any(lin.bias is None for lin in m.master_linears()):
+            raise ValueError(f"model {i}: a layer without bias")
+        if arch(m) != arch(models[0]):
+            raise ValueError(f"model {i}: " + mismatch.format(arch(m), arch(models[0])))
+        if versus_first is not None:
+            versus_first(i, m, models[0])
+    return models
+
+
 class EnsembleStep:
+    def __init__(self, models, problem_params, device):
+        """`models`: what the engine's `check_models` returned"""
+        _lib.require_device()
+        self.models, self.problem_params, self.device = models, problem_params, torch.device(device)
+        # (one single-model engine per model: problem cache, LazyLinear materialisation, the upper bound and the observation rows
+        # are theirs; they allocate nothing until they run, and they never run here)
+        self._engines = [FusedRollout(m, problem_params, device) for m in models]
+        self.last_kernels = {}          # launch class -> kernel name the library recorded in the last run
+        self.weights = self.grad = self._grad_views = None   # [K][P], [K][>= P]: once per engine
+        self.param_shapes = None        # shapes of one model's parameters in `parameters()` order (EnsembleAdam's `param_shapes`)
+        self._bind_requested = self._bound = False
+        self._dims_bound = None         # layer sizes, once the parameters are bound
+        self.best_dev = self.best_weights = None   # `fit`: [K] lowest dev loss so far, [K][P] the parameters that gave it
+
+    @property
+    def n_models(self):
+        return len(self.models)
+
+    def _note(self, tag):
+        name = _lib.lib().nic_last_kernel()
+        self.last_kernels[tag] = name.decode() if name else None
+
+    # ---- the models' layers and the rows of `weights` -------------------------------------------------------------------------------------
+    def _materialize(self, F):
+        """(every model's layers, their common sizes [F, H1, ..., n_out]), LazyLinear first layers materialised for F inputs"""
+        for eng in self._engines:
+            eng.materialize(F)
+        lins = [eng._linears() for eng in self._engines]
+        dims = [[ls[0].in_features] + [m.out_features for m in ls] for ls in lins]
+        for i, d in enumerate(dims):
+            if d != dims[0]:
+                raise ValueError(f"model {i}: layer sizes {d} differ from model 0's {dims[0]}")
+        return lins, dims[0]
+
+    def _layers(self, F):
+        """(layers, sizes) a step on F input rows runs with; bound: (None, the bound sizes) - nothing is packed, and the per-model
+        checks were made when the parameters were bound"""
+        return (None, self._dims_bound) if self._bound else self._materialize(F)
+
+    def _model_buffers(self, dims):
+        """`weights [K][P]` for these layer sizes.  Other sizes than before (a LazyLinear model materialised anew) allocate again,
+        and the gradient buffer goes with them; bound parameters cannot change theirs."""
+        P = packed_count(dims)
+        if self.weights is None or self.weights.shape[1] != P:
+            if self._bound:
+                raise ValueError(f"{type(self).__name__}: layer sizes {list(dims)} differ from the bound parameters'")
+            self.weights, self.grad, self._grad_views = torch.zeros(self.n_models, P, device=self.device), None, None
+            self.param_shapes = [shape for _, n, k, _ in layer_slices(dims) for shape in ((n, k), (n,))]
+
+    def _bind(self, lins, dims):
+        """weight.data / bias.data of every layer <- views of the model's row of `weights`, which gets the current values once"""
+        pack_ensemble_weights(lins, self.weights)
+        for m, ls in enumerate(lins):
+            row = self.weights[m]
+            for lin, (o, n, k, bo) in zip(ls, layer_slices(dims)):
+                lin.weight.data = row[o:o + n * k].view(n, k)
+                lin.bias.data = row[bo:bo + n]
+        self._bound, self._dims_bound = True, list(dims)
+
+    def bind_parameters(self):
+        """Opt-in: from now on the models' parameters LIVE in `weights [K][P]` (views of their rows), `run` and `train_step` pack
+        nothing, and whatever writes a parameter in place - `load_state_dict`, an optimizer - writes the packed row.  Binds now if
+        the input width is known (a materialised first layer), else on the first batch."""
+        self._bind_requested = True
+        F = materialized_width(self.models)
+        if F is not None and not self._bound:
+            lins, dims = self._materialize(F)
+            self._model_buffers(dims)
+            self._bind(lins, dims)
+
+    def _ready_weights(self, lins, dims, optimizer):
+        """A step, once the engine's `_setup` sized `weights` and before anything is launched: the optimizer must be one for (K, P);
+        then `weights` gets the parameters - bound, they live there; bind requested, they do from this first batch on; else they
+        are packed, every run (the caller's optimizers moved them)."""
+        if optimizer is not None:
+            self._require_optimizer_shape(optimizer)
+        if self._bound:
+            return
+        if self._bind_requested:
+            self._bind(lins, dims)
+        else:
+            pack_ensemble_weights(lins, self.weights)
+
+    def param_grads(self):
+        """[(parameter, gradient view into the [K][P] buffer of the last training run)] over all models"""
+        out = []
+        for eng, (gw, gb) in zip(self._engines, self._grad_views):
+            for i, m in enumerate(eng._linears()):
+                out += [(m.weight, gw[i]), (m.bias, gb[i])]
+        return out
+
+    # ---- the frames of `run` and `train_step`; `batch`: the engine's `_step` arguments before train, discrete_allocation, optimizer -----
+    def _run(self, batch, train, accumulate_grads, discrete_allocation):
+        if discrete_allocation and train:
+            raise ValueError("discrete_allocation is an evaluation-time option of the fused rollout")
+        tt = self._step(*batch, train=train, discrete_allocation=discrete_allocation, optimizer=None)
+        if train:
+            sr.assign_grads(self.param_grads(), accumulate_grads)
+        return tt[:, 0], tt[:, 1]
+
+    def _train_step(self, batch, optimizer):
+        self._require_step(optimizer)
+        tt = self._step(*batch, train=True, discrete_allocation=False, optimizer=optimizer)
+        return tt[:, 0], tt[:, 1]
+
     def _require_step(self, optimizer):
         """`train_step`'s preconditions that need no device: bound parameters, an EnsembleAdam"""
         who = type(self).__name__

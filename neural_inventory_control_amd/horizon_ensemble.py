@@ -20,10 +20,12 @@ single-model calls instead (4 K GEMM launches + 6 K around them).
 `run` alone leaves the optimizer to the caller and packs all K models' weights again every call.  The whole training step is
 `train_step`: after `bind_parameters()` every model's `weight` / `bias` are views of its row of `weights [K][P]`, nothing is packed,
 and an `EnsembleAdam(K, P)` updates all K rows with two launches - no per-model Python.  `fit` is the epoch loop over `train_step`
-with the best weights per model kept on the device (ensemble_step.py, shared with `SmallPolicyEnsemble`).
+with the best weights per model kept on the device.  Packing, binding, the frames of `run` / `train_step`, `fit` and the generic
+model checks are `EnsembleStep`'s (ensemble_step.py, shared with `SmallPolicyEnsemble`); this module has the policy's rules, the
+buffers of a batch shape and the launches.
 
-Layout: weights `[K][P]` in `nn.Linear`'s own order (per layer the weight, row-major, then the bias; packed with one `torch.cat`
-per run unless the parameters are bound), gradients `[K][P]` in the same order (`param.grad` are views of it),
+Layout: weights `[K][P]` in `nn.Linear`'s own order (ensemble_step.py's packed row: per layer the weight, row-major, then the bias;
+packed with one `torch.cat` per run unless the parameters are bound), gradients `[K][P]` in the same order (`param.grad` are views of it),
 inputs `X [K][F][T][ldb]` (the kernel writes model m's state rows into X[m]; the observation rows are model-independent, filled once
 and copied), `z1_obs [K][H1][T][ldb]`, costs `rewards [K][T][ldb]`, histories and pre-activation gradients `[K][rows][T][ldb]`.
 
@@ -37,119 +39,35 @@ import torch
 from . import _lib, ops
 from . import horizon_rollout as hz
 from . import small_rollout as sr
-from .ensemble_step import bind_rows, EnsembleStep, materialized_width
+from .ensemble_step import (check_model_list, EnsembleStep, grad_views, layer_slices,  # noqa: F401  (the last two: re-exports)
+                            packed_count, pack_ensemble_weights)
 from .layout import demand_trace_soa, Table
 from .rollout import _pad32, FusedRollout
-from .small_ensemble import pack_ensemble_weights
-
-MAX_MODELS = 65535
 
 
 def _layer_sizes(model):
     a = model.nn_args
-    return tuple(a["neurons_per_hidden_layer"]["master"]) + (a["output_sizes"]["master"],)
+    return list(a["neurons_per_hidden_layer"]["master"]) + [a["output_sizes"]["master"]]
 
 
 def check_models(models):
     """The models an ensemble takes: 1 <= K <= 65535 `data_driven` policies `FusedRollout` takes, with the same layer sizes (two
     hidden layers: what the whole-horizon kernels run) and a bias in every layer.  ValueError names the first mismatch.  Host-side
     only; the setting's side of `HorizonPlan.supports` is checked when the first batch arrives."""
-    models = list(models)
-    if len(models) < 1:
-        raise ValueError("HorizonPolicyEnsemble needs at least one model")
-    if len(models) > MAX_MODELS:
-        raise ValueError("HorizonPolicyEnsemble takes at most 65,535 models")
-    for i, m in enumerate(models):
-        name = getattr(m, "nn_args", {}).get("name") if hasattr(m, "nn_args") else None
-        if name != "data_driven" or not FusedRollout.supports(m):
-            raise ValueError(f"model {i}: HorizonPolicyEnsemble handles the data_driven policy (ELU inside, ReLU on the output), got {name!r}")
-        if _layer_sizes(m) != _layer_sizes(models[0]):
-            raise ValueError(f"model {i}: layer sizes {list(_layer_sizes(m))} differ from model 0's {list(_layer_sizes(models[0]))}")
-        if any(lin.bias is None for lin in m.master_linears()):
-            raise ValueError(f"model {i}: a layer without bias")
-    return models
-
-
-def layer_slices(dims):
-    """[(weight offset, rows, cols, bias offset)] per layer of one model's packed row; dims = [F, H1, ..., n_out]"""
-    out, off = [], 0
-    for k, n in zip(dims[:-1], dims[1:]):
-        out.append((off, n, k, off + n * k))
-        off += n * k + n
-    return out
-
-
-def packed_count(dims):
-    return sum(n * k + n for k, n in zip(dims[:-1], dims[1:]))
-
-
-def grad_views(grad, dims):
-    """[(weight gradients per layer, bias gradients per layer)] per model: views into grad [K][>= P] in the packed-weight layout"""
-    sl = layer_slices(dims)
-    return [([grad[m, o:o + n * k].view(n, k) for o, n, k, _ in sl], [grad[m, bo:bo + n] for _, n, _, bo in sl])
-            for m in range(grad.shape[0])]
+    return check_model_list(models, "HorizonPolicyEnsemble", ("data_driven",), "the data_driven policy (ELU inside, ReLU on the output)",
+                            _layer_sizes, "layer sizes {} differ from model 0's {}")
 
 
 class HorizonPolicyEnsemble(EnsembleStep):
     def __init__(self, models, problem_params, device):
-        self.models = check_models(models)
-        _lib.require_device()
-        self.problem_params = problem_params
-        self.device = torch.device(device)
-        # (one single-model engine per model: problem cache, LazyLinear materialisation and the observation rows are theirs; they
-        # allocate nothing until they run, and they never run here)
-        self._engines = [FusedRollout(m, problem_params, device) for m in self.models]
-        self.last_kernels = {}   # launch class -> kernel name the library recorded in the last run
+        super().__init__(check_models(models), problem_params, device)
         self._key = None
         self.plan = self.prob = None
-        self.weights = self.grad = self._grad_views = None   # [K][P], [K][P]
         self.model_gemms = True         # one GEMM launch for all K models where the library takes the shape; False: the per-model loop
-        self.param_shapes = None        # shapes of one model's parameters in `parameters()` order (EnsembleAdam's `param_shapes`)
-        self._bind_requested = self._bound = False
-        self._dims_bound = None         # layer sizes, once the parameters are bound
-        self.best_dev = self.best_weights = None   # `fit`: [K] lowest dev loss so far, [K][P] the parameters that gave it
-
-    @property
-    def n_models(self):
-        return len(self.models)
-
-    def _dims(self, F):
-        for eng in self._engines:
-            eng.materialize(F)
-        lins = [eng._linears() for eng in self._engines]
-        dims = [[ls[0].in_features] + [m.out_features for m in ls] for ls in lins]
-        for i, d in enumerate(dims):
-            if d != dims[0]:
-                raise ValueError(f"model {i}: layer sizes {d} differ from model 0's {dims[0]}")
-        return lins, dims[0]
-
-    def _model_buffers(self, dims):
-        P = packed_count(dims)
-        if self.weights is None or self.weights.shape[1] != P:
-            if self._bound:
-                raise ValueError(f"HorizonPolicyEnsemble: layer sizes {list(dims)} differ from the bound parameters'")
-            self.weights, self.grad, self._grad_views = torch.zeros(self.n_models, P, device=self.device), None, None
-            self.param_shapes = [shape for _, n, k, _ in layer_slices(dims) for shape in ((n, k), (n,))]
-
-    def _bind(self, lins, dims):
-        """weight.data / bias.data of every layer <- views of the model's row of `weights`, which gets the current values once"""
-        pack_ensemble_weights(lins, self.weights)
-        bind_rows(lins, self.weights, layer_slices(dims))
-        self._bound, self._dims_bound = True, list(dims)
-
-    def bind_parameters(self):
-        """Opt-in: from now on the models' parameters LIVE in `weights [K][P]` (views of their rows), `run` and `train_step` pack
-        nothing, and whatever writes a parameter in place - `load_state_dict`, an optimizer - writes the packed row.  Binds now if
-        the input width is known (a materialised first layer), else on the first batch."""
-        self._bind_requested = True
-        F = materialized_width(self.models)
-        if F is not None and not self._bound:
-            lins, dims = self._dims(F)
-            self._model_buffers(dims)
-            self._bind(lins, dims)
 
     def _setup(self, prob, T, train, dims, shift):
         K, dev, ld = self.n_models, self.device, prob.ldb
+        z = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
         key = (prob.B, T, K, tuple(dims), prob.S, prob.Wn, prob.Ws, prob.Ww, shift)
         if self._key != key:
             self._key = None
@@ -160,7 +78,6 @@ class HorizonPolicyEnsemble(EnsembleStep):
                 raise ValueError(f"HorizonPolicyEnsemble: the whole-horizon kernels do not take this setting / policy (layer sizes {dims}, "
                                  f"{FD} state rows, {prob.B} scenarios x {T} periods)")
             self.plan = hz.HorizonPlan(prob, dims)
-            z = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
             self._model_buffers(dims)
             self.F, self.F_dyn, self.dims = F, FD, list(dims)
             self.state0 = z(FD, ld)
@@ -187,7 +104,6 @@ class HorizonPolicyEnsemble(EnsembleStep):
             self._key = key
         if train and self.hist is None:
             # the training buffers come with the first training run of a shape and stay: evaluation runs in between use the rest
-            z = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
             n_cols = T * ld
             rows = [dims[1], dims[2], dims[3], self.plan.n_ord + prob.Wn]   # h1, h2, logits, orders (+ shipped)
             self.hist = [z(K, r, T, ld) for r in rows]
@@ -216,18 +132,6 @@ class HorizonPolicyEnsemble(EnsembleStep):
             self._strides = (bool(train), hz.ensemble_strides(self.n_models, **st))
         return self._strides[1]
 
-    def param_grads(self):
-        """[(parameter, gradient view into the [K][P] buffer of the last training run)] over all models"""
-        out = []
-        for eng, (gw, gb) in zip(self._engines, self._grad_views):
-            for i, m in enumerate(eng._linears()):
-                out += [(m.weight, gw[i]), (m.bias, gb[i])]
-        return out
-
-    def _note(self, tag):
-        name = _lib.lib().nic_last_kernel()
-        self.last_kernels[tag] = name.decode() if name else None
-
     # ---- one batch ---------------------------------------------------------------------------------------------------------------
     def run(self, data, periods, ignore_periods=0, train=True, observation_params=None, grad_scale=None, accumulate_grads=False,
             discrete_allocation=False):
@@ -235,23 +139,16 @@ class HorizonPolicyEnsemble(EnsembleStep):
         into one [K][P] gradient buffer, `accumulate_grads` adds - `small_rollout.assign_grads`).  Arguments as `FusedRollout.run`.
         Returns (total [K], reported [K]) device tensors; `rewards` [K][T][ldb] holds the per-period costs.  A setting the
         whole-horizon kernels do not take is a ValueError: there is no fall-back to K single steps."""
-        if discrete_allocation and train:
-            raise ValueError("discrete_allocation is an evaluation-time option of the fused rollout")
-        tt = self._step(data, periods, ignore_periods, train, observation_params, grad_scale, discrete_allocation, None)
-        if train:
-            sr.assign_grads(self.param_grads(), accumulate_grads)
-        return tt[:, 0], tt[:, 1]
+        return self._run((data, periods, ignore_periods, observation_params, grad_scale), train, accumulate_grads, discrete_allocation)
 
     def train_step(self, data, periods, ignore_periods=0, optimizer=None, observation_params=None, grad_scale=None):
         """One whole training step of all K models: forward, the cost reduction, backward, the batched weight gradients and
         `optimizer.step(self.weights, self.grad)` (an `EnsembleAdam` over this engine's (K, P)) - no packing, no `param.grad`, no
         per-model Python.  Needs `bind_parameters()`.  Returns (total [K], reported [K]) of the step BEFORE the update, as `run`
         does."""
-        self._require_step(optimizer)
-        tt = self._step(data, periods, ignore_periods, True, observation_params, grad_scale, False, optimizer)
-        return tt[:, 0], tt[:, 1]
+        return self._train_step((data, periods, ignore_periods, observation_params, grad_scale), optimizer)
 
-    def _step(self, data, periods, ignore_periods, train, observation_params, grad_scale, discrete_allocation, optimizer):
+    def _step(self, data, periods, ignore_periods, observation_params, grad_scale, train, discrete_allocation, optimizer):
         lead, dev, K = self._engines[0], self.device, self.n_models
         if not FusedRollout.observation_ok(self.models[0], observation_params, data):
             raise ValueError("data_driven needs a past-demand window and the days_from_christmas time feature")
@@ -261,12 +158,9 @@ class HorizonPolicyEnsemble(EnsembleStep):
         P_ = observation_params["demand"]["past_periods"]
         FD = prob.S * prob.Ws + prob.Wn * prob.Ww
         F = FD + prob.S * P_ + 2 * prob.S + data["days_from_christmas"].shape[1] + prob.S * data["lead_times"].shape[2]
-        if self._bound:   # (nothing is packed, and the per-model checks were made when the parameters were bound)
-            lins, dims = None, self._dims_bound
-            if dims[0] != F:
-                raise ValueError(f"HorizonPolicyEnsemble: this batch gives the policy {F} input rows, the bound parameters have {dims[0]}")
-        else:
-            lins, dims = self._dims(F)
+        lins, dims = self._layers(F)
+        if self._bound and dims[0] != F:
+            raise ValueError(f"HorizonPolicyEnsemble: this batch gives the policy {F} input rows, the bound parameters have {dims[0]}")
         if prob.E != 0 or len(dims) != 4:
             raise ValueError(f"HorizonPolicyEnsemble: the whole-horizon kernels do not take this setting / policy (layer sizes {dims}, "
                              f"{prob.E} extra echelons)")
@@ -274,13 +168,8 @@ class HorizonPolicyEnsemble(EnsembleStep):
         if demand_soa.shape[0] < T + shift:
             raise ValueError("Current period is greater than the number of periods in the data")
         self._setup(prob, T, train, dims, shift)
-        if optimizer is not None:
-            self._require_optimizer_shape(optimizer)
+        self._ready_weights(lins, dims, optimizer)
         Fo, n_cols = F - FD, T * ld
-        if self._bind_requested and not self._bound:
-            self._bind(lins, dims)
-        if not self._bound:
-            pack_ensemble_weights(lins, self.weights)   # (every run: the optimizers moved the parameters)
         batched = self.model_gemms and self._models_ok
         P, sl = self.weights.shape[1], layer_slices(dims)
         a = prob.S * prob.Ws

@@ -21,7 +21,12 @@ dividing K, and model m then runs on instance m // (K // I) - its own demand tra
 hyper-parameter grid over a setting (one_store_lost.yml: underage_cost 4, 9, 19, 39) x seeds in one engine.  The instances share B,
 the trace length, the pipeline shape (lead times may differ within it) and the flags; `check_instances` names the first mismatch.
 The engine owns the instance-stacked inputs per batch shape (demand [I][T_total][1][ldb], state0 [I][F][ldb], one stacked tensor
-per table) at fixed addresses, so a replayed step stages and pins nothing.  A plain dict is the one-batch path, unchanged.
+per table) at fixed addresses, so a replayed step stages and pins nothing.  A plain dict is the one-batch path.  Either kind of
+input is only staged differently (`_stage_batch`, `_stage_instances`): from the descriptor on, `_step` is one path.
+
+The packed-row layout, binding, the frames of `run` / `train_step`, `fit` and the generic model checks are `EnsembleStep`'s
+(ensemble_step.py, shared with `HorizonPolicyEnsemble`); this module has the small policies' rules, the batch shapes' buffers
+and their launch replay, the staging and the launches.
 
 YAML / `main_run` wiring, a `torch.library` operator and multi-GPU sharding are not part of this engine.
 """
@@ -29,12 +34,11 @@ import copy
 
 import torch
 
-from . import _lib
 from . import small_rollout as sr
-from .ensemble_step import bind_rows, EnsembleStep, materialized_width
+from .ensemble_step import check_model_list, EnsembleStep, grad_views, pack_ensemble_weights  # noqa: F401  (the last: a re-export)
 from .launch_replay import LaunchReplay, ReplayedEngine
 from .layout import demand_trace_soa, EnvProblem, Table
-from .rollout import _HEADS, FusedRollout
+from .rollout import _HEADS, FusedRollout  # noqa: F401  (`FusedRollout`: a re-export)
 
 SMALL_POLICIES = ("vanilla_one_store", "vanilla_serial")
 
@@ -44,33 +48,28 @@ def _upper_bound(model):
     return float(ub.reshape(-1)[0]) if torch.is_tensor(ub) else float(ub)
 
 
+def _arch(m):
+    a = m.nn_args
+    return (a["name"], tuple(a["neurons_per_hidden_layer"]["master"]), a["output_sizes"]["master"])
+
+
+def _hidden_rule(i, m):
+    hidden = _arch(m)[1]
+    if not (1 <= len(hidden) <= 3 and all(w == sr.H for w in hidden)):
+        raise ValueError(f"model {i}: the whole-horizon kernels take 1..3 hidden layers of {sr.H} neurons, got {list(hidden)}")
+
+
+def _upper_bound_rule(i, m, first):
+    if _arch(m)[0] == "vanilla_serial" and _upper_bound(m) != _upper_bound(first):
+        raise ValueError(f"model {i}: warehouse_upper_bound {_upper_bound(m)} differs from model 0's {_upper_bound(first)}")
+
+
 def check_models(models):
     """The models an ensemble takes: K >= 1 policies `FusedRollout`'s small route takes, of one architecture - the same policy,
     layer sizes (1..3 hidden layers of 32, the same head) and `warehouse_upper_bound`.  ValueError names the first mismatch.
     Host-side only; the setting's side of `SmallRolloutPlan.supports` is checked when the first batch arrives."""
-    models = list(models)
-    if len(models) < 1:
-        raise ValueError("SmallPolicyEnsemble needs at least one model")
-    if len(models) > 65535:
-        raise ValueError("SmallPolicyEnsemble takes at most 65,535 models")
-
-    def arch(m):
-        a = m.nn_args
-        return (a["name"], tuple(a["neurons_per_hidden_layer"]["master"]), a["output_sizes"]["master"])
-    for i, m in enumerate(models):
-        name = getattr(m, "nn_args", {}).get("name") if hasattr(m, "nn_args") else None
-        if name not in SMALL_POLICIES or not FusedRollout.supports(m):
-            raise ValueError(f"model {i}: SmallPolicyEnsemble handles the ELU MLP policies {SMALL_POLICIES}, got {name!r}")
-        hidden = arch(m)[1]
-        if not (1 <= len(hidden) <= 3 and all(w == sr.H for w in hidden)):
-            raise ValueError(f"model {i}: the whole-horizon kernels take 1..3 hidden layers of {sr.H} neurons, got {list(hidden)}")
-        if any(lin.bias is None for lin in m.master_linears()):
-            raise ValueError(f"model {i}: a layer without bias")
-        if arch(m) != arch(models[0]):
-            raise ValueError(f"model {i}: architecture {arch(m)} differs from model 0's {arch(models[0])}")
-        if name == "vanilla_serial" and _upper_bound(m) != _upper_bound(models[0]):
-            raise ValueError(f"model {i}: warehouse_upper_bound {_upper_bound(m)} differs from model 0's {_upper_bound(models[0])}")
-    return models
+    return check_model_list(models, "SmallPolicyEnsemble", SMALL_POLICIES, f"the ELU MLP policies {SMALL_POLICIES}", _arch,
+                            "architecture {} differs from model 0's {}", _hidden_rule, _upper_bound_rule)
 
 
 def check_instances(probs, n_models, trace_lengths=None):
@@ -122,22 +121,6 @@ def stack_instance_tables(probs):
     return stacked, strides
 
 
-def pack_ensemble_weights(linears_per_model, out=None):
-    """[K][P]: row m = `pack_weights` of model m's layers, all K models in ONE torch.cat (one launch)."""
-    K = len(linears_per_model)
-    flat = sr.pack_weights([lin for lins in linears_per_model for lin in lins], None if out is None else out.view(-1))
-    if flat.numel() % K != 0:
-        raise ValueError("pack_ensemble_weights: the models do not have the same number of parameters")
-    return flat.view(K, -1) if out is None else out
-
-
-def grad_views(grad, F, n_hidden, n_out):
-    """[(weight gradients per layer, bias gradients per layer)] per model: views into grad [K][>= P] in the packed-weight layout."""
-    sl = sr.layer_slices(F, n_hidden, n_out)
-    return [([grad[m, o:o + n * k].view(n, k) for o, n, k, _ in sl], [grad[m, bo:bo + n] for _, n, _, bo in sl])
-            for m in range(grad.shape[0])]
-
-
 class _ShapeState:
     """What ONE batch shape (the key of `_setup`) owns: the buffers sized for it and the launch-replay state whose captures hold
     their addresses, its staged demand trace and its pinned problem.  Weights, gradients and optimizer state depend on (K, P)
@@ -160,33 +143,17 @@ _MAX_KEPT_SHAPES = 4   # other batch shapes kept while their launches are replay
 
 class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
     def __init__(self, models, problem_params, device):
-        self.models = check_models(models)
-        _lib.require_device()
-        self.problem_params = problem_params
-        self.device = torch.device(device)
+        super().__init__(check_models(models), problem_params, device)   # (`grad` here: [K][P rounded up to 4])
         self.head = _HEADS[self.models[0].nn_args["name"]]
-        # (one single-model engine per model: problem cache, LazyLinear materialisation and the upper bound are theirs; they
-        # allocate nothing until they run)
-        self._engines = [FusedRollout(m, problem_params, device) for m in self.models]
         self.small_lane_scenarios = 0   # 16 or 32 scenarios per wavefront (0: small_rollout.lane_width's rule)
-        self.last_kernels = {}          # launch class -> kernel name the library recorded in the last run
         self._key = None
         self._shape = _ShapeState(False)   # the current batch shape's buffers and LaunchReplay (read as `ens.rewards`, `ens.plan`, ...)
         self._shapes = {}               # key -> _ShapeState of the other shapes whose launches are replayed
-        self.weights = self.grad = self._grad_views = None   # [K][P], [K][P rounded up to 4]: once per engine
-        self.param_shapes = None        # shapes of one model's parameters in `parameters()` order (EnsembleAdam's `param_shapes`)
-        self._bind_requested = self._bound = False
-        self._dims_bound = None         # layer sizes, once the parameters are bound
-        self.best_dev = self.best_weights = None   # `fit`: [K] lowest dev loss so far, [K][P] the parameters that gave it
 
     def __getattr__(self, name):   # (only reached for names the engine itself does not have)
         if name in _ShapeState.FIELDS:
             return getattr(self._shape, name)
         raise AttributeError(name)
-
-    @property
-    def n_models(self):
-        return len(self.models)
 
     # ---- launch mode: `use_graph` True / False / "auto" (launch_replay.py) is the engine's, the rest is per batch shape -----------------
     _replay = property(lambda self: self._shape.replay)
@@ -203,46 +170,7 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
         for st in self._shapes.values():
             st.replay.use_graph = value
 
-    # ---- buffers: weights and gradients once per engine, the rest once per (B, T, K) ---------------------------------------------------
-    def _model_buffers(self, dims):
-        n_hidden, n_out = len(dims) - 2, dims[-1]
-        P = sr.packed_weight_count(dims[0], n_hidden, n_out)
-        if self.weights is None:
-            self.weights = torch.zeros(self.n_models, P, device=self.device)
-            self.param_shapes = [shape for _, n, k, _ in sr.layer_slices(dims[0], n_hidden, n_out) for shape in ((n, k), (n,))]
-        assert self.weights.shape[1] == P   # (the models' layer sizes are fixed once they are materialised)
-
-    def _bind(self, lins, dims):
-        """weight.data / bias.data of every layer <- views of the model's row of `weights`, which gets the current values once"""
-        pack_ensemble_weights(lins, self.weights)
-        bind_rows(lins, self.weights, sr.layer_slices(dims[0], len(dims) - 2, dims[-1]))
-        self._bound, self._dims_bound = True, dims
-
-    def bind_parameters(self):
-        """Opt-in: from now on the models' parameters LIVE in `weights [K][P]` (views of their rows), `run` and `train_step` pack
-        nothing, and whatever writes a parameter in place - `load_state_dict`, an optimizer - writes the packed row.  Binds now if
-        the input width is known (a materialised first layer), else on the first batch."""
-        self._bind_requested = True
-        known = materialized_width(self.models)
-        if known is not None and not self._bound:
-            lins = self._materialized(known)
-            dims = self._dims(lins)
-            self._model_buffers(dims)
-            self._bind(lins, dims)
-
-    def _materialized(self, F):
-        for eng in self._engines:
-            eng.materialize(F)
-        return [eng._linears() for eng in self._engines]
-
-    @staticmethod
-    def _dims(lins):
-        dims = [[ls[0].in_features] + [m.out_features for m in ls] for ls in lins]
-        for i, d in enumerate(dims):
-            if d != dims[0]:
-                raise ValueError(f"model {i}: layer sizes {d} differ from model 0's {dims[0]}")
-        return dims[0]
-
+    # ---- buffers: weights and gradients once per engine (ensemble_step.py), the rest once per (B, T, K) -------------------------------
     def _switch_shape(self, key):
         """Batch shape `key` becomes the current one.  The outgoing shape is kept while its launches are replayed (its captures
         hold its buffers' addresses; an epoch alternates between a few shapes), else its buffers are released before the new
@@ -256,31 +184,24 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
         self._key = key
 
     def _setup(self, prob, T, train, instances=()):
-        """Sizes what this batch needs; returns the models' layers (None once the parameters are bound: nothing is packed, and the
-        per-model checks were made when they were bound).  `instances`: what the key of a list-of-instances batch carries besides
-        the shape (I, the trace length, the tables' layouts); a one-batch run has none."""
+        """Sizes what this batch needs; returns the models' layers (None once the parameters are bound) and their sizes, for
+        `_ready_weights`.  `instances`: what the key of a list-of-instances batch carries besides the shape (I, the trace length,
+        the tables' layouts); a one-batch run has none."""
         K, dev, ld = self.n_models, self.device, prob.ldb
+        z = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
         F = prob.S * prob.Ws + (0 if self.head == "softplus" else prob.Wn * prob.Ww + prob.E * prob.We)
-        if self._bound:
-            lins, dims = None, self._dims_bound
-        else:
-            lins = self._materialized(F)
-            dims = self._dims(lins)
+        lins, dims = self._layers(F)
         if dims[0] != F or not sr.SmallRolloutPlan.supports(prob, self.head, dims):
             raise ValueError(f"SmallPolicyEnsemble: the whole-horizon kernels do not take this setting / policy (layer sizes {dims}, "
                              f"{F} state rows)")
-        if not self._bound:
+        if not self._bound:   # (bound: sized when they were bound, and `dims` are theirs)
             self._model_buffers(dims)
-            if self._bind_requested:
-                self._bind(lins, dims)
-                lins = None
         key = (prob.B, T, K, tuple(dims), prob.Ws, prob.Wn, prob.Ww, prob.E, prob.We) + tuple(instances)
         if self._key != key:
             self._switch_shape(key)
         sh = self._shape
         if sh.plan is None:
             sh.plan = plan = sr.SmallRolloutPlan(prob, self.head, dims)
-            z = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
             sh.state0 = z(F, ld)
             sh.rewards, sh.final = z(K, T, ld), z(K, F, ld)
             sh.totals = z(K, 2)
@@ -295,51 +216,32 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
         if train and sh.states is None:
             # the training buffers come with the first training run of a shape and stay: evaluation runs in between use the rest
             s = sh.slices
-            z = lambda *s_: torch.zeros(*s_, device=dev)  # noqa: E731
             sh.states, sh.hidden, sh.logits = z(K, s["states"]), z(K, s["hidden"]), z(K, s["logits"])
             sh.slab = z(K, s["slab_rows"], s["slab_row_stride"])
             sh.g_reward, sh.g_reward_key = z(ld), None
             if self.grad is None:   # (with the engine's first training run, and kept: it depends on (K, P) only)
                 self.grad = z(K, s["grad"])
-                self._grad_views = grad_views(self.grad, F, sh.plan.n_hidden, sh.plan.n_out)
+                self._grad_views = grad_views(self.grad, dims)
             sh.strides.update(states=s["states"], hidden=s["hidden"], logits=s["logits"], slab=s["slab"], grad=s["grad"])
             sh.ens = sr.ensemble_strides(K, **sh.strides)
-        return lins
+        return lins, dims
 
-    def param_grads(self):
-        """[(parameter, gradient view into the [K][P] buffer of the last training run)] over all models"""
-        out = []
-        for eng, (gw, gb) in zip(self._engines, self._grad_views):
-            for i, m in enumerate(eng._linears()):
-                out += [(m.weight, gw[i]), (m.bias, gb[i])]
-        return out
-
-    def _note(self, tag):
-        name = _lib.lib().nic_last_kernel()
-        self.last_kernels[tag] = name.decode() if name else None
-
-    # ---- one batch ---------------------------------------------------------------------------------------------------------------
+    # ---- one batch, or one batch per instance -----------------------------------------------------------------------------------------
     def run(self, data, periods, ignore_periods=0, train=True, observation_params=None, demand_soa=None, grad_scale=None,
             accumulate_grads=False, discrete_allocation=False):
         """Rollout of one batch - or, `data` a list of I batches, of instance m // (K // I)'s batch - under every model (and, if
         `train`, d(mean loss)/d(theta) into every model's `param.grad`: views
         into one [K][P] gradient buffer, `accumulate_grads` adds - `small_rollout.assign_grads`).  Arguments as
         `FusedRollout.run`.  Returns (total [K], reported [K]) device tensors; `rewards` [K][T][ldb] holds the per-period costs."""
-        if discrete_allocation and train:
-            raise ValueError("discrete_allocation is an evaluation-time option of the fused rollout")
-        tt = self._step(data, periods, ignore_periods, train, observation_params, demand_soa, grad_scale, discrete_allocation, None)
-        if train:
-            sr.assign_grads(self.param_grads(), accumulate_grads)
-        return tt[:, 0], tt[:, 1]
+        return self._run((data, periods, ignore_periods, observation_params, demand_soa, grad_scale), train, accumulate_grads,
+                         discrete_allocation)
 
     def train_step(self, data, periods, ignore_periods=0, optimizer=None, observation_params=None, demand_soa=None, grad_scale=None):
         """One whole training step of all K models (on one batch, or on a list of I instances' batches as in `run`): forward,
         backward, the reduction's two launches and `optimizer`'s two (an
         `EnsembleAdam` over this engine's (K, P)) - no packing, no `param.grad`, no per-model Python.  Needs `bind_parameters()`.
         Returns (total [K], reported [K]) of the step BEFORE the update, as `run` does."""
-        self._require_step(optimizer)
-        tt = self._step(data, periods, ignore_periods, True, observation_params, demand_soa, grad_scale, False, optimizer)
-        return tt[:, 0], tt[:, 1]
+        return self._train_step((data, periods, ignore_periods, observation_params, demand_soa, grad_scale), optimizer)
 
     def _fill_state0(self, state0, prob, data):
         """state0 [F][ldb] <- the batch's initial pipelines in the reference's cat(flatten(...)) order"""
@@ -353,95 +255,44 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
                 state0[b:b + prob.E * prob.We].view(prob.E, prob.We, -1)[:, :, :B].copy_(
                     data["initial_echelon_inventories"].permute(1, 2, 0))
 
-    def _step(self, data, periods, ignore_periods, train, observation_params, demand_soa, grad_scale, discrete_allocation, optimizer):
-        if isinstance(data, (list, tuple)):
-            return self._step_instances(data, periods, ignore_periods, train, observation_params, demand_soa, grad_scale,
-                                        discrete_allocation, optimizer)
-        lead, dev, K = self._engines[0], self.device, self.n_models
-        prob = lead._problem_for(data)
-        T, B, ld = periods, prob.B, prob.ldb
-        shift = observation_params["demand"]["period_shift"] if observation_params else 0
+    # ---- staging: what differs between the two kinds of input.  Each returns (the problem, demand trace and initial state the
+    # descriptor points at), the NicSmallInstances or None, and what the input adds to the captures' variant and to their key --------------
+    def _stage_batch(self, data, T, shift, train, demand_soa, optimizer):
+        """One batch for all K models.  A captured sequence holds raw pointers: it reads the pinned problem's tables and the staged
+        demand trace, refreshed in place."""
+        prob = self._engines[0]._problem_for(data)
         if demand_soa is None:
-            demand_soa = demand_trace_soa(data["demands"], ld, dev)
+            demand_soa = demand_trace_soa(data["demands"], prob.ldb, self.device)
         if demand_soa.shape[0] < T + shift:
             raise ValueError("Current period is greater than the number of periods in the data")
-        lins = self._setup(prob, T, train)
-        if optimizer is not None:
-            self._require_optimizer_shape(optimizer)
+        self._ready_weights(*self._setup(prob, T, train), optimizer)
         sh = self._shape
-        replay = sh.replay
-        # a captured sequence holds raw pointers: it reads the pinned problem's tables and the staged demand trace, refreshed in place
-        prob = replay.pin_problem(prob)
-        demand_soa = replay.stage_demand(demand_soa)
-        if not self._bound:
-            pack_ensemble_weights(lins, self.weights)   # (every run: the optimizers moved the parameters)
+        prob = sh.replay.pin_problem(prob)
+        demand_soa = sh.replay.stage_demand(demand_soa)
         self._fill_state0(sh.state0, prob, data)
-        ub = lead._ub() if self.head != "softplus" else 0.0
-        width = sr.lane_width(self.small_lane_scenarios, train, B)
-        desc = sh.plan.desc(T, shift, self.weights, demand_soa, sh.state0, ub, round_orders=discrete_allocation, prob=prob,
-                            lane_scenarios=width)
-        hist = (sh.states, sh.hidden, sh.logits) if train else (None, None, None)
-        n_el = T * ld
-        if train:
-            if grad_scale is None:
-                grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
-            sh.g_reward_key = sr.set_g_reward(sh.g_reward, B, grad_scale, sh.g_reward_key)
+        return (prob, demand_soa, sh.state0), None, (), ()
 
-        def launches():
-            sr.small_rollout_ensemble_fwd(desc, sh.ens, sh.rewards, sh.final, *hist)
-            self._note("fwd")
-            if train:
-                row = sh.slab.shape[2]
-                sr.small_rollout_ensemble_bwd_wgrad(desc, sh.ens, *hist, Table(sh.g_reward, 0, 1), sh.slab, row)
-                self._note("bwd")
-                sr.small_rollout_ensemble_reduce(sh.ens, sh.slab, sr.slab_rows_written(B, width), row, self.grad.shape[1], self.grad,
-                                                 sh.rewards, n_el, ignore_periods * ld, sh.totals, sh.scratch)
-            else:   # the same reduction, costs only: an evaluation pass returns the very bits a training pass does
-                sr.small_rollout_ensemble_reduce(sh.ens, None, 0, 0, 0, None, sh.rewards, n_el, ignore_periods * ld, sh.totals,
-                                                 sh.scratch)
-            self._note("reduce")
-            if optimizer is not None:
-                optimizer.step(self.weights, self.grad)
-
-        # what a captured sequence bakes in besides this shape's buffers.  Engine-wide things are the `variant` (a change drops this
-        # shape's captures now, another shape's when it is current again); the optimizer's buffers, which only a training step's
-        # sequence holds, are part of the capture's key, so evaluations in between (`fit`) change nothing
-        if replay.on():
-            replay.set_variant((K, self.small_lane_scenarios, self.weights.data_ptr(), ub))
-        opt_key = optimizer and tuple(t.data_ptr() for t in (optimizer.hyper, optimizer.state, optimizer.coef, optimizer.exp_avg,
-                                                               optimizer.exp_avg_sq))
-        replay.probe_begin(train)
-        replay.call((train, opt_key, ignore_periods, shift, bool(discrete_allocation), width), launches)
-        replay.probe_end()
-        replay.ran()
-        return sh.totals.clone()   # (outside the capture: the caller's tensors must not change under a later step)
-
-    def _step_instances(self, datas, periods, ignore_periods, train, observation_params, demand_soa, grad_scale, discrete_allocation,
-                        optimizer):
-        """`_step` for a list of I batches: model m runs on datas[m // (K // I)].  The instances' inputs are copied into this batch
-        shape's stacked buffers (the tables only when the batches present other tensors than last time), whose addresses a captured
-        sequence keeps: nothing is pinned or staged."""
-        lead, dev, K = self._engines[0], self.device, self.n_models
-        I = len(datas)
+    def _stage_instances(self, datas, T, shift, train, demand_soa, optimizer):
+        """A list of I batches: model m runs on datas[m // (K // I)].  The instances' inputs are copied into this batch shape's
+        stacked buffers (the tables only when the batches present other tensors than last time), whose addresses a captured
+        sequence keeps: nothing is pinned or staged.  A caller's demand_soa is read in place, so its address is part of the
+        capture's key."""
+        lead, dev, K, I = self._engines[0], self.device, self.n_models, len(datas)
         if I < 1 or K % I != 0:   # (before anything is built from the batches)
             raise ValueError(f"SmallPolicyEnsemble: {I} problem instances do not divide {K} models")
         probs = [lead._problem_for(data) for data in datas]
         lengths = [int(data["demands"].shape[2]) for data in datas]
         check_instances(probs, K, lengths)
         prob0 = probs[0]
-        T, B, ld, T_total = periods, prob0.B, prob0.ldb, lengths[0]
-        shift = observation_params["demand"]["period_shift"] if observation_params else 0
+        B, ld, T_total = prob0.B, prob0.ldb, lengths[0]
         if T_total < T + shift:
             raise ValueError("Current period is greater than the number of periods in the data")
         if demand_soa is not None and tuple(demand_soa.shape) != (I, T_total, 1, ld):
             raise ValueError(f"SmallPolicyEnsemble: demand_soa of a list of instances must be [I][T_total][1][ldb] = {(I, T_total, 1, ld)}, "
                              f"got {tuple(demand_soa.shape)}")
         layouts = tuple((name, getattr(prob0, name).scn_stride) for name in EnvProblem._TABLES if getattr(prob0, name).tensor is not None)
-        lins = self._setup(prob0, T, train, instances=("instances", I, T_total, layouts))
-        if optimizer is not None:
-            self._require_optimizer_shape(optimizer)
+        self._ready_weights(*self._setup(prob0, T, train, instances=("instances", I, T_total, layouts)), optimizer)
         sh = self._shape
-        replay = sh.replay
         F = sh.plan.F
         if sh.inst_state0 is None:
             sh.inst_state0 = torch.zeros(I, F, ld, device=dev)
@@ -461,13 +312,23 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
             demand_soa = sh.inst_demand
             for i, data in enumerate(datas):
                 demand_soa[i, :, :, :B].copy_(data["demands"].permute(2, 1, 0))
-        if not self._bound:
-            pack_ensemble_weights(lins, self.weights)   # (every run: the optimizers moved the parameters)
         for i, data in enumerate(datas):
             self._fill_state0(sh.inst_state0[i], prob0, data)
-        ub = lead._ub() if self.head != "softplus" else 0.0
+        return (sh.inst_prob, demand_soa, sh.inst_state0), sh.inst, (I,), (I, demand_soa.data_ptr())
+
+    def _step(self, data, periods, ignore_periods, observation_params, demand_soa, grad_scale, train, discrete_allocation, optimizer):
+        """`data` a dict: all K models on one batch (`nic_small_rollout_ensemble_*`); a list or tuple of I dicts: model m on its
+        instance's (`nic_small_rollout_instances_*`, also for I = 1).  The kind of input decides the staging, the launch pair's
+        entry points and what it adds to the captures' variant and key; the rest is one path."""
+        K, T = self.n_models, periods
+        shift = observation_params["demand"]["period_shift"] if observation_params else 0
+        stage = self._stage_instances if isinstance(data, (list, tuple)) else self._stage_batch
+        (prob, demand_soa, state0), inst, variant, key = stage(data, T, shift, train, demand_soa, optimizer)
+        sh, B, ld = self._shape, prob.B, prob.ldb
+        replay = sh.replay
+        ub = self._engines[0]._ub() if self.head != "softplus" else 0.0
         width = sr.lane_width(self.small_lane_scenarios, train, B)
-        desc = sh.plan.desc(T, shift, self.weights, demand_soa, sh.inst_state0, ub, round_orders=discrete_allocation, prob=sh.inst_prob,
+        desc = sh.plan.desc(T, shift, self.weights, demand_soa, state0, ub, round_orders=discrete_allocation, prob=prob,
                             lane_scenarios=width)
         hist = (sh.states, sh.hidden, sh.logits) if train else (None, None, None)
         n_el = T * ld
@@ -475,30 +336,36 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
             if grad_scale is None:
                 grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
             sh.g_reward_key = sr.set_g_reward(sh.g_reward, B, grad_scale, sh.g_reward_key)
+        if inst is None:
+            fwd, bwd_wgrad, where = sr.small_rollout_ensemble_fwd, sr.small_rollout_ensemble_bwd_wgrad, (desc, sh.ens)
+        else:
+            fwd, bwd_wgrad, where = sr.small_rollout_instances_fwd, sr.small_rollout_instances_bwd_wgrad, (desc, sh.ens, inst)
 
         def launches():
-            sr.small_rollout_instances_fwd(desc, sh.ens, sh.inst, sh.rewards, sh.final, *hist)
+            fwd(*where, sh.rewards, sh.final, *hist)
             self._note("fwd")
             if train:
                 row = sh.slab.shape[2]
-                sr.small_rollout_instances_bwd_wgrad(desc, sh.ens, sh.inst, *hist, Table(sh.g_reward, 0, 1), sh.slab, row)
+                bwd_wgrad(*where, *hist, Table(sh.g_reward, 0, 1), sh.slab, row)
                 self._note("bwd")
                 sr.small_rollout_ensemble_reduce(sh.ens, sh.slab, sr.slab_rows_written(B, width), row, self.grad.shape[1], self.grad,
                                                  sh.rewards, n_el, ignore_periods * ld, sh.totals, sh.scratch)
-            else:
+            else:   # the same reduction, costs only: an evaluation pass returns the very bits a training pass does
                 sr.small_rollout_ensemble_reduce(sh.ens, None, 0, 0, 0, None, sh.rewards, n_el, ignore_periods * ld, sh.totals,
                                                  sh.scratch)
             self._note("reduce")
             if optimizer is not None:
                 optimizer.step(self.weights, self.grad)
 
-        # (as in `_step`; a caller's demand_soa is read in place, so its address is part of the capture's key)
+        # what a captured sequence bakes in besides this shape's buffers.  Engine-wide things are the `variant` (a change drops this
+        # shape's captures now, another shape's when it is current again); the optimizer's buffers, which only a training step's
+        # sequence holds, are part of the capture's key, so evaluations in between (`fit`) change nothing
         if replay.on():
-            replay.set_variant((K, I, self.small_lane_scenarios, self.weights.data_ptr(), ub))
+            replay.set_variant((K,) + variant + (self.small_lane_scenarios, self.weights.data_ptr(), ub))
         opt_key = optimizer and tuple(t.data_ptr() for t in (optimizer.hyper, optimizer.state, optimizer.coef, optimizer.exp_avg,
                                                                optimizer.exp_avg_sq))
         replay.probe_begin(train)
-        replay.call((train, opt_key, ignore_periods, shift, bool(discrete_allocation), width, I, demand_soa.data_ptr()), launches)
+        replay.call((train, opt_key, ignore_periods, shift, bool(discrete_allocation), width) + key, launches)
         replay.probe_end()
         replay.ran()
-        return sh.totals.clone()
+        return sh.totals.clone()   # (outside the capture: the caller's tensors must not change under a later step)

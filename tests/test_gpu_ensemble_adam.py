@@ -15,7 +15,7 @@ import pytest
 import torch
 
 import ensemble_adam_checks as eac
-from neural_inventory_control_amd import _lib, small_ensemble as se, small_rollout as sr, workloads
+from neural_inventory_control_amd import _lib, ensemble_step as es, small_rollout as sr, workloads
 from neural_inventory_control_amd.data_handling import Scenario
 from neural_inventory_control_amd.ensemble_adam import EnsembleAdam
 from neural_inventory_control_amd.neural_networks import NeuralNetworkCreator
@@ -200,7 +200,7 @@ def _write_back(ens):
     """an unbound engine's packed rows -> its models' parameters (what K optimizers on the parameters would have done)"""
     F, nh, no = ens.plan.F, ens.plan.n_hidden, ens.plan.n_out
     with torch.no_grad():
-        for model, (ws, bs) in zip(ens.models, se.grad_views(ens.weights, F, nh, no)):
+        for model, (ws, bs) in zip(ens.models, es.grad_views(ens.weights, [F] + [sr.H] * nh + [no])):
             for lin, w, b in zip(model.master_linears(), ws, bs):
                 lin.weight.copy_(w)
                 lin.bias.copy_(b)

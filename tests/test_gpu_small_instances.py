@@ -417,6 +417,41 @@ def test_three_train_steps_equal_per_instance_ensembles(use_graph):
     assert not torch.equal(ens.weights[0], ens.weights[R])
 
 
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_one_batch_and_instance_steps_interleaved_equal_a_fresh_engine_per_step(use_graph):
+    """One engine takes a dict, a list, a dict, a list (evaluation, the batches of the step before it, then new ones) through its
+    one step path; its twin is a fresh eager engine for EVERY step on the twin's models and the twin's EnsembleAdam, so nothing of
+    one step - initial state, pinned problem, stacked tables, captures - can reach the next.  40 scenarios leave padded lanes."""
+    I, R, B, T = 2, 2, 40, 8
+    K = I * R
+    setting, obs, lists = _engine_instances("cfg1", I, B, T, 4)
+    steps = [(lists[0][1], True), (lists[1], True), (lists[2][0], True), (lists[1], False), (lists[3], True)]
+    lrs = (1e-2, 3e-3, 1e-3, 3e-2)
+    models = _fresh_models("cfg1", 4 * I * B, T, (61, 62, 63, 64))
+    alone = _clones(models)
+    ens = SmallPolicyEnsemble(models, setting["problem_params"], DEV)
+    ens.use_graph = use_graph
+    ens.bind_parameters()
+    opt, topt = _adam(ens, lrs), None
+    for step, (data, train) in enumerate(steps):
+        twin = SmallPolicyEnsemble(alone, setting["problem_params"], DEV)
+        twin.bind_parameters()   # (the values the step before left in the twin's models)
+        topt = _adam(twin, lrs) if topt is None else topt
+        if train:
+            got, want = ens.train_step(data, T, IGN, opt, obs), twin.train_step(data, T, IGN, topt, obs)
+        else:
+            got, want = (e.run(data, T, IGN, train=False, observation_params=obs) for e in (ens, twin))
+        torch.cuda.synchronize()
+        assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]), step
+        assert torch.equal(ens.weights, twin.weights), step
+        assert ("instances" in ens.last_kernels["fwd"]) == isinstance(data, list), (step, ens.last_kernels)
+        assert ens.last_kernels["fwd"] == twin.last_kernels["fwd"]
+    assert torch.equal(opt.exp_avg, topt.exp_avg) and torch.equal(opt.exp_avg_sq, topt.exp_avg_sq)
+    assert opt.steps().tolist() == [4] * K and not torch.equal(ens.weights[0], ens.weights[R])
+    if use_graph:   # (the dict shape's second step and both of the list shape's later ones were replayed)
+        assert len(ens._shapes) == 1 and sum(len(st.replay.graphs) for st in [ens._shape, *ens._shapes.values()]) == 3
+
+
 def test_fit_over_lists_of_instances_returns_histories_per_model():
     I, R, B, T = 2, 2, 64, 6
     K = I * R

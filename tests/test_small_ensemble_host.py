@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from golden_io import Golden
-from neural_inventory_control_amd import _lib, build, small_ensemble as se, small_rollout as sr
+from neural_inventory_control_amd import _lib, build, ensemble_step as es, small_ensemble as se, small_rollout as sr
 from neural_inventory_control_amd.neural_networks import NeuralNetworkCreator
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -224,7 +224,7 @@ def test_gradient_views_map_to_the_right_parameter_of_the_right_model(name):
     P0 = sr.packed_weight_count(F, nh, no)
     grad = torch.full((3, (P0 + 3) // 4 * 4 + 8), float("nan"))
     grad[:, :P0] = se.pack_ensemble_weights(lins)
-    views = se.grad_views(grad, F, nh, no)
+    views = es.grad_views(grad, [F] + [sr.H] * nh + [no])
     assert len(views) == 3
     for ls, (gw, gb) in zip(lins, views):
         assert len(gw) == len(gb) == len(ls)
@@ -232,6 +232,16 @@ def test_gradient_views_map_to_the_right_parameter_of_the_right_model(name):
             assert w.shape == lin.weight.shape and b.shape == lin.bias.shape
             assert torch.equal(w, lin.weight.detach()) and torch.equal(b, lin.bias.detach())
             assert w.data_ptr() >= grad.data_ptr() and w._base is not None   # views, not copies
+
+
+@pytest.mark.parametrize("F", [1, 3, 7])
+@pytest.mark.parametrize("nh", [1, 2, 3])
+@pytest.mark.parametrize("no", [1, 2])
+def test_the_two_descriptions_of_the_packed_row_agree(F, nh, no):
+    """ensemble_step's layout on dims = [F, 32, ..., n_out] is small_rollout's on (F, n_hidden, n_out)"""
+    dims = [F] + [32] * nh + [no]
+    assert es.layer_slices(dims) == sr.layer_slices(F, nh, no)
+    assert es.packed_count(dims) == sr.packed_weight_count(F, nh, no)
 
 
 def test_model_lists_that_are_refused_without_a_device():
