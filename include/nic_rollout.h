@@ -627,8 +627,8 @@ int nic_horizon_rollout_bwd(const NicHorizonDesc* d, const float* state_hist, co
  * single-model kernels above on its own W1 / W2 / W3 / b2 / b3 and z1_obs and writes its own rewards, final state, histories and dz
  * buffers: model m's copy of each starts m * its stride floats behind model 0's, which is what the descriptor (weights) and the
  * arguments (buffers) point at, and has exactly the single-model layout.  state0, the demand trace, the adjacency mask, the cost and
- * lead-time tables, g_reward, hist_stride, T, t0 and the flags are shared.  Every model's numbers are the bits of a single-model
- * call on its slice.  Only head_mode 0 (the MLP) has this form: a tape has no weights.
+ * lead-time tables, g_reward, hist_stride, T, t0 and the flags are shared (nic_horizon_rollout_instances_* below gives every
+ * model its problem instance's state0, trace and tables).  Every model's numbers are the bits of a single-model call on its slice.  Only head_mode 0 (the MLP) has this form: a tape has no weights.
  * Strides are in floats; csrc/horizon_ensemble_plan.h gives the slice sizes (nic_horizon_rollout_ensemble_slices) and the checks:
  * 1 <= n_models <= 65535, no negative stride, every stride of a buffer that is passed >= its slice, the strides of z1_obs, the
  * rewards, the final state, the histories and the dz buffers multiples of 4 floats (the GEMMs and the reduction that take a
@@ -661,6 +661,40 @@ int nic_horizon_rollout_ensemble_fwd(const NicHorizonDesc* d, const NicHorizonEn
 int nic_horizon_rollout_ensemble_bwd(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const float* state_hist, const float* h1_hist,
                                      const float* h2_hist, const float* logits_hist, const float* orders_hist, NicTable2 g_reward,
                                      float* dz1_hist, float* dz2_hist, float* dz3_hist, void* stream);
+
+/* ---- K data_driven policies on I problem instances: the same launch pair, each model reading ITS instance's inputs ---------------
+ * The K models are I instances x R = K / I replicas (I divides K): model m runs on instance m / R (the grid stays (x, K); the
+ * kernels get m / R from one scalar multiply and shift).  An instance is a demand trace, an initial state and the six static
+ * tables the kernels stage (io.underage, io.holding, io.lead_times, io.wh_holding, io.wh_lead_times, io.wh_edge_costs); instance
+ * i's copy of each starts i * stride floats behind instance 0's, which is what the descriptor and the state0 argument point at.
+ * Stride 0 = shared by all instances; all strides 0 with I = 1 is nic_horizon_rollout_ensemble_* exactly (its entry points pass
+ * just that).  The adjacency mask (the setting's topology), g_reward, B, ldb, T, t0, the pipeline shape (lead times may differ per
+ * instance within it), hist_stride, the flags and all of NicHorizonEnsemble are shared.  Every model's numbers are the bits of a
+ * single-model call on its weights and its instance's inputs.
+ * The checks are csrc/horizon_ensemble_plan.h's (horizon_instances_check): 1 <= n_instances <= 65535 dividing n_models, R <= 65535,
+ * no negative stride, a non-zero demand stride >= (t0 + T) * S * ldb (no period past t0 + T - 1 is read), a non-zero state0 stride
+ * >= F_dyn * ldb, both multiples of 4 floats, a non-zero table stride >= what the table's loc / sup / scn strides span over its
+ * rows and B scenarios, no stride for a table whose pointer is NULL.  A refused request returns non-zero, leaves a message in
+ * nic_last_error and launches nothing - before anything touches the device.  The cost reduction is per model already:
+ * nic_small_rollout_ensemble_reduce as it is. */
+typedef struct NicHorizonInstances {
+    int32_t n_instances, reserved;
+    int64_t demand, state0;                /* traces [I][>= (t0 + T) * S * ldb], initial states [I][>= F_dyn * ldb] */
+    int64_t underage, holding, lead;       /* the tables, in NicEnvStepIO's order */
+    int64_t wh_holding, wh_lead, wh_edge;
+} NicHorizonInstances;
+/* K forward rollouts on I instances in one launch (trainer.py:181-216, `simulate_batch`, once per model and setting, under
+ * DataDrivenNet.forward, neural_networks.py:430-515); buffers as nic_horizon_rollout_ensemble_fwd, state0 instance 0's. */
+int nic_horizon_rollout_instances_fwd(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* inst,
+                                      const float* z1_obs, const float* state0, float* rewards, float* state_final,
+                                      float* state_hist, float* h1_hist, float* h2_hist, float* logits_hist, float* orders_hist,
+                                      void* stream);
+/* K backward sweeps on I instances in one launch (trainer.py:181-216 under `backward`, once per model and setting; the adjoint of
+ * neural_networks.py:430-515); buffers as nic_horizon_rollout_ensemble_bwd.  g_reward is shared. */
+int nic_horizon_rollout_instances_bwd(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* inst,
+                                      const float* state_hist, const float* h1_hist, const float* h2_hist,
+                                      const float* logits_hist, const float* orders_hist, NicTable2 g_reward, float* dz1_hist,
+                                      float* dz2_hist, float* dz3_hist, void* stream);
 
 /* ---- fused three-layer 32-wide MLP over gathered inputs (graph policies) -----------------------------------------
  * The GNN policy (neural_networks.py:742-1492) applies five small MLPs (`gnn.yml`: K -> 32 -> 32 -> 32 or 1, ELU inside) to

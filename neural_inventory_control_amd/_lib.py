@@ -120,6 +120,15 @@ class NicHorizonEnsembleSlices(C.Structure):
     _fields_ = [(n, C.c_int64) for n in HORIZON_ENSEMBLE_BUFFERS]
 
 
+HORIZON_INSTANCE_FIELDS = ("demand", "state0", "underage", "holding", "lead", "wh_holding", "wh_lead", "wh_edge")
+
+
+class NicHorizonInstances(C.Structure):
+    """I problem instances under one whole-horizon ensemble launch: floats between two instances' demand traces, initial states
+    and tables (0: shared; include/nic_rollout.h)"""
+    _fields_ = [("n_instances", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_int64) for n in HORIZON_INSTANCE_FIELDS]
+
+
 class NicClosedFormDesc(C.Structure):
     _fields_ = ([(n, C.c_int32) for n in (
         "n_scenarios", "ldb", "T", "t0", "ignore_periods", "policy", "n_levels", "S", "Ws", "Wn", "Ww", "E", "We",
@@ -258,6 +267,11 @@ PROTOTYPES = {
                                                    _vp, _vp, _vp, _vp]),
     "nic_horizon_rollout_ensemble_bwd": (C.c_int, [C.POINTER(NicHorizonDesc), C.POINTER(NicHorizonEnsemble), _vp, _vp, _vp, _vp, _vp,
                                                    NicTable2, _vp, _vp, _vp, _vp]),
+    "nic_horizon_rollout_instances_fwd": (C.c_int, [C.POINTER(NicHorizonDesc), C.POINTER(NicHorizonEnsemble),
+                                                    C.POINTER(NicHorizonInstances), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nic_horizon_rollout_instances_bwd": (C.c_int, [C.POINTER(NicHorizonDesc), C.POINTER(NicHorizonEnsemble),
+                                                    C.POINTER(NicHorizonInstances), _vp, _vp, _vp, _vp, _vp, NicTable2, _vp, _vp, _vp,
+                                                    _vp]),
     "nic_gnn_alloc_env_fwd": (C.c_int, [_IOP, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "nic_gnn_alloc_env_bwd": (C.c_int, [_IOP, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, NicTable2, _vp, _vp, _vp, _vp, _vp]),
     "nic_gnn_period_pack_size": (C.c_int, [_i32, _i32]),

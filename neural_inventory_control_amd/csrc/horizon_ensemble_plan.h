@@ -138,4 +138,111 @@ NIC_HE_FN int horizon_ensemble_check_bwd(const NicHorizonDesc& d, const NicHoriz
 // ---- the kernels' side: model m's pointer advance ------------------------------------------------------------------------------
 NIC_HE_FN int64_t horizon_model_offset(uint32_t model, int64_t stride) { return (int64_t)model * stride; }
 
+// ---- I problem instances (nic_horizon_rollout_instances_*) -------------------------------------------------------------------------
+// The K models are I instances x R replicas: model m (grid y, as in every ensemble launch) reads instance m / R's demand trace,
+// initial state and the six tables hz_stage_tables stages, each `instance x stride` floats behind instance 0's (stride 0: shared).
+// The advance is made once, at entry, beside the per-model one, as 64-bit pointer arithmetic: every 32-bit element offset formed
+// afterwards is an offset inside ONE instance's slice, so check_offsets bounds what it bounds for one instance, whatever I is.
+// The grid stays (x, K): the kernels get m / R from one scalar multiply and shift by a constant the launcher computes (the rule of
+// csrc/small_ensemble_plan.h, whose third grid dimension cost the small forward 18 VGPRs): for m, R < 2^16,
+// (m * ceil(2^32 / R)) >> 32 == m / R exactly.  blockIdx.y and the constant are scalars, so the instance index is wave-uniform
+// and the advances stay on the scalar unit.
+// The demand slice is (t0 + T) * S * ldb: neither kernel reads period t0 + T (the forward's last prefetch re-reads period
+// t0 + T - 1, the backward fetches period t - 1 only while t > 0), so nothing of instance i + 1's trace is read for instance i.
+constexpr int kHiTables = 6;   // underage, holding, lead_times, wh_holding, wh_lead_times, wh_edge_costs (NicEnvStepIO's order)
+NIC_HE_FN int horizon_instance_replicas(int n_models, int n_instances) { return n_models / n_instances; }
+NIC_HE_FN uint32_t horizon_instance_of(uint32_t model, uint32_t replicas) { return model / replicas; }   // the rule
+NIC_HE_FN uint64_t horizon_instance_magic(int replicas) { return ((1ull << 32) + (uint64_t)replicas - 1) / (uint64_t)replicas; }
+NIC_HE_FN uint32_t horizon_instance_by_magic(uint32_t model, uint64_t magic) { return (uint32_t)(((uint64_t)model * magic) >> 32); }   // what the kernels run
+NIC_HE_FN int64_t horizon_instance_offset(uint32_t instance, int64_t stride) { return (int64_t)instance * stride; }
+NIC_HE_FN NicHorizonInstances horizon_instances_shared() { return NicHorizonInstances{1, 0, 0, 0, 0, 0, 0, 0, 0, 0}; }
+NIC_HE_FN int64_t horizon_instance_table_stride(const NicHorizonInstances& in, int k) {
+    const int64_t s[kHiTables] = {in.underage, in.holding, in.lead, in.wh_holding, in.wh_lead, in.wh_edge};
+    return s[k];
+}
+NIC_HE_FN const float* horizon_instance_table_ptr(const NicEnvStepIO& io, int k) {
+    const float* p[kHiTables] = {io.underage.p, io.holding.p, io.lead_times.p, io.wh_holding.p, io.wh_lead_times.p, io.wh_edge_costs.p};
+    return p[k];
+}
+// floats from a table's first element to one past the last the kernels address for `rows` locations (x `sups` suppliers) and B scenarios
+NIC_HE_FN int64_t horizon_span(int64_t n, int64_t stride) { return (n - 1) * (stride < 0 ? -stride : stride); }
+NIC_HE_FN int64_t horizon_table2_extent(const NicTable2& t, int rows, int B) {
+    return rows > 0 ? horizon_span(rows, t.loc_stride) + horizon_span(B, t.scn_stride) + 1 : 0;
+}
+NIC_HE_FN int64_t horizon_table3_extent(const NicTable3& t, int rows, int sups, int B) {
+    return rows > 0 ? horizon_span(rows, t.loc_stride) + horizon_span(sups, t.sup_stride) + horizon_span(B, t.scn_stride) + 1 : 0;
+}
+NIC_HE_FN int64_t horizon_instance_table_extent(const NicHorizonDesc& d, int k) {
+    const NicEnvDims& D = d.io.dims;
+    const int S = D.n_stores, Wn = D.n_warehouses, B = D.n_scenarios;
+    switch (k) {
+        case 0: return horizon_table2_extent(d.io.underage, S, B);
+        case 1: return horizon_table2_extent(d.io.holding, S, B);
+        case 2: return horizon_table3_extent(d.io.lead_times, S, Wn > 0 ? Wn : 1, B);
+        case 3: return horizon_table2_extent(d.io.wh_holding, Wn, B);
+        case 4: return horizon_table2_extent(d.io.wh_lead_times, Wn, B);
+        default: return horizon_table2_extent(d.io.wh_edge_costs, Wn, B);
+    }
+}
+NIC_HE_FN int64_t horizon_instance_demand_slice(const NicHorizonDesc& d) {
+    return ((int64_t)d.t0 + d.T) * d.io.dims.n_stores * d.io.dims.ldb;
+}
+NIC_HE_FN int64_t horizon_instance_state0_slice(const NicHorizonDesc& d) {
+    const NicEnvDims& D = d.io.dims;
+    return ((int64_t)D.n_stores * D.store_slots + (int64_t)D.n_warehouses * D.warehouse_slots) * D.ldb;
+}
+// the six tables of the descriptor <- instance `instance`'s.  A NULL table has stride 0 (horizon_instances_check): it stays NULL.
+NIC_HE_FN void horizon_instance_tables(NicEnvStepIO& io, const NicHorizonInstances& in, uint32_t instance) {
+    io.underage.p += horizon_instance_offset(instance, in.underage);
+    io.holding.p += horizon_instance_offset(instance, in.holding);
+    io.lead_times.p += horizon_instance_offset(instance, in.lead);
+    io.wh_holding.p += horizon_instance_offset(instance, in.wh_holding);
+    io.wh_lead_times.p += horizon_instance_offset(instance, in.wh_lead);
+    io.wh_edge_costs.p += horizon_instance_offset(instance, in.wh_edge);
+}
+
+enum HorizonInstancesRefusal {
+    HI_OK = 0, HI_COUNT, HI_DIVIDE, HI_GRID, HI_NEGATIVE, HI_DEMAND, HI_STATE0, HI_ALIGN, HI_NULL_TABLE, HI_UNDERAGE, HI_HOLDING, HI_LEAD,
+    HI_WH_HOLDING, HI_WH_LEAD, HI_WH_EDGE,
+};
+NIC_HE_FN const char* horizon_instances_reason(int r) {
+    switch (r) {
+        case HI_OK: return "accepted";
+        case HI_COUNT: return "n_instances must be 1..65535";
+        case HI_DIVIDE: return "n_instances must divide n_models";
+        case HI_GRID: return "the replicas per instance must be at most 65535";
+        case HI_NEGATIVE: return "negative instance stride";
+        case HI_DEMAND: return "demand stride shorter than (t0 + T) * S * ldb";
+        case HI_STATE0: return "state0 stride shorter than the state rows x ldb";
+        case HI_ALIGN: return "the strides of demand and state0 must be multiples of 4 floats";
+        case HI_NULL_TABLE: return "instance stride for a table whose pointer is NULL";
+        case HI_UNDERAGE: return "underage stride shorter than the table";
+        case HI_HOLDING: return "holding stride shorter than the table";
+        case HI_LEAD: return "lead-time stride shorter than the table";
+        case HI_WH_HOLDING: return "warehouse-holding stride shorter than the table";
+        case HI_WH_LEAD: return "warehouse-lead-time stride shorter than the table";
+        case HI_WH_EDGE: return "warehouse-edge-cost stride shorter than the table";
+        default: return "?";
+    }
+}
+// `d`: the request's descriptor (t0, T, the dims and the tables with their strides)
+NIC_HE_FN int horizon_instances_check(const NicHorizonInstances& in, int n_models, const NicHorizonDesc& d) {
+    if (in.n_instances < 1 || in.n_instances > kHeMaxModels) return HI_COUNT;
+    if (n_models % in.n_instances != 0) return HI_DIVIDE;
+    if (horizon_instance_replicas(n_models, in.n_instances) > kHeMaxModels) return HI_GRID;
+    if (in.demand < 0 || in.state0 < 0) return HI_NEGATIVE;
+    for (int k = 0; k < kHiTables; ++k)
+        if (horizon_instance_table_stride(in, k) < 0) return HI_NEGATIVE;
+    if (in.demand != 0 && in.demand < horizon_instance_demand_slice(d)) return HI_DEMAND;
+    if (in.state0 != 0 && in.state0 < horizon_instance_state0_slice(d)) return HI_STATE0;
+    if (in.demand % 4 != 0 || in.state0 % 4 != 0) return HI_ALIGN;
+    for (int k = 0; k < kHiTables; ++k) {
+        const int64_t stride = horizon_instance_table_stride(in, k);
+        if (stride == 0) continue;
+        if (horizon_instance_table_ptr(d.io, k) == nullptr) return HI_NULL_TABLE;
+        if (stride < horizon_instance_table_extent(d, k)) return HI_UNDERAGE + k;
+    }
+    return HI_OK;
+}
+
 }  // namespace nic

@@ -262,14 +262,20 @@ __device__ __forceinline__ f32x4 layer64(const float (&aW)[16], const float* hx,
     return acc + acc1;
 }
 
-// K models in one launch (nic_horizon_rollout_ensemble_*): the kernels' first argument.  Without the flag it IS the descriptor (the
-// same kernel-argument bytes, and `if constexpr` leaves the single-model instantiations the code they were); with it the strides
-// come along, and model m = blockIdx.y advances its weight pointers and its buffers ONCE, at entry, by m x stride as 64-bit pointer
-// arithmetic - every 32-bit element offset below stays an offset inside one model's slice (check_offsets).  Shared by all models:
-// state0, the demand trace, the mask, the tables, g_reward.
+// K models in one launch (nic_horizon_rollout_ensemble_* / _instances_*): the kernels' first argument.  Without the flag it IS the
+// descriptor (the same kernel-argument bytes, and `if constexpr` leaves the single-model instantiations the code they were); with it
+// the strides come along, and model m = blockIdx.y advances its weight pointers and its buffers ONCE, at entry, by m x stride as
+// 64-bit pointer arithmetic - every 32-bit element offset below stays an offset inside one model's slice (check_offsets).
+// Problem instances, DESIGN (a) of the two the plan header weighs: the instance strides ride in HzArgs<true> for EVERY ensemble launch
+// and the kernels add instance x stride unconditionally, beside the per-model advance - d.demand, state0 (forward) and the `p` of
+// the six tables hz_stage_tables reads; nic_horizon_rollout_ensemble_* passes all-zero strides with I = 1.  No third instantiation,
+// no kernel added to the build.  The grid stays (x, K): instance = m / R by one scalar multiply and shift (`magic`, from the
+// launcher), wave-uniform, so the advances stay on the scalar unit.  Shared by all instances: the mask, g_reward, everything else.
+// Demand: neither kernel reads period t0 + T (the forward's last prefetch is clamped to t0 + T - 1, the backward fetches t - 1
+// only while t > 0), so an instance's slice is (t0 + T) * S * ldb and no read reaches the next instance's trace.
 template <bool ENS> struct HzArgs;
 template <> struct HzArgs<false> { NicHorizonDesc d; };
-template <> struct HzArgs<true> { NicHorizonDesc d; NicHorizonEnsemble e; };
+template <> struct HzArgs<true> { NicHorizonDesc d; NicHorizonEnsemble e; NicHorizonInstances in; uint64_t magic; };
 template <class T> __device__ __forceinline__ T* hz_model(T* p, uint32_t model, int64_t stride) {   // (NULL stays NULL: "not passed")
     return p ? p + nic::horizon_model_offset(model, stride) : p;
 }
@@ -305,6 +311,10 @@ __global__ __launch_bounds__(kThreads, (MAXS1 == 16 || HZ_FORCE_OCC2) ? 2 : 1) v
         h2_hist = hz_model(h2_hist, m, e.h2_hist);
         logits_hist = hz_model(logits_hist, m, e.logits_hist);
         orders_hist = hz_model(orders_hist, m, e.orders_hist);
+        const uint32_t inst = nic::horizon_instance_by_magic(m, a.magic);   // (scalar: blockIdx.y and a kernel argument)
+        d.demand += nic::horizon_instance_offset(inst, a.in.demand);
+        state0 += nic::horizon_instance_offset(inst, a.in.state0);
+        nic::horizon_instance_tables(d.io, a.in, inst);
     }
     const NicEnvDims& D = d.io.dims;
     const HzIds I = hz_ids();
@@ -584,6 +594,9 @@ __global__ __launch_bounds__(kThreads, (VAR == 0 || HZ_FORCE_OCC2) ? 2 : 1) void
         dz1_hist = hz_model(dz1_hist, m, e.dz1);
         dz2_hist = hz_model(dz2_hist, m, e.dz2);
         dz3_hist = hz_model(dz3_hist, m, e.dz3);
+        const uint32_t inst = nic::horizon_instance_by_magic(m, a.magic);
+        d.demand += nic::horizon_instance_offset(inst, a.in.demand);
+        nic::horizon_instance_tables(d.io, a.in, inst);
     }
     const NicEnvDims& D = d.io.dims;
     const HzIds I = hz_ids();
@@ -851,9 +864,16 @@ int allow_lds(K kernel, int bytes, const char* who) {
     return 0;
 }
 
+// what an ensemble launch carries besides the descriptor: `in` == nullptr is one instance shared by all models (all-zero strides)
+HzArgs<true> hz_ensemble_args(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* in) {
+    const NicHorizonInstances one = in ? *in : nic::horizon_instances_shared();
+    return HzArgs<true>{*d, *e, one, nic::horizon_instance_magic(nic::horizon_instance_replicas(e->n_models, one.n_instances))};
+}
+
 // The two launchers.  e == nullptr: the single-model kernels (grid y = 1, the descriptor alone); else the ensemble instantiations, one
-// grid row per model, after csrc/horizon_ensemble_plan.h's checks - a refused request launches nothing.
-int launch_fwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsemble* e, const float* z1_obs, const float* state0,
+// grid row per model, after csrc/horizon_ensemble_plan.h's checks - a refused request launches nothing, and is refused before
+// anything touches the device.  in != nullptr (with e): model m reads instance m / R's demand, state0 and tables.
+int launch_fwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* in, const float* z1_obs, const float* state0,
                float* rewards, float* state_final, float* state_hist, float* h1_hist, float* h2_hist, float* logits_hist,
                float* orders_hist, void* stream) {
     if (int r = validate(d, who)) return r;
@@ -864,6 +884,8 @@ int launch_fwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsembl
     if (e) {
         const int why = nic::horizon_ensemble_check_fwd(*d, *e, nic::horizon_ensemble_slices(*d), state_final != nullptr, state_hist != nullptr);
         NIC_REQUIRE(why == 0, "%s: %s (%d models)", who, nic::horizon_ensemble_reason(why), e->n_models);
+        const int why_in = in ? nic::horizon_instances_check(*in, e->n_models, *d) : 0;
+        NIC_REQUIRE(why_in == 0, "%s: %s (%d models, %d instances)", who, nic::horizon_instances_reason(why_in), e->n_models, in->n_instances);
     }
     const NicEnvDims& D = d->io.dims;
     const int FD = D.n_stores * D.store_slots + D.n_warehouses * D.warehouse_slots;
@@ -872,13 +894,14 @@ int launch_fwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsembl
     const dim3 grid(nic::ceil_div(D.n_scenarios, NB), e ? e->n_models : 1), block(kThreads);
     hipStream_t s = nic::as_stream(stream);
     const int steps = fwd_steps(FD);
-    if (e) nic::note_kernelf("horizon_fwd_kernel<8,%d,models=%d>", steps, e->n_models);
+    if (e && in) nic::note_kernelf("horizon_fwd_kernel<8,%d,models=%d,instances=%d>", steps, e->n_models, in->n_instances);
+    else if (e) nic::note_kernelf("horizon_fwd_kernel<8,%d,models=%d>", steps, e->n_models);
     else nic::note_kernelf("horizon_fwd_kernel<8,%d>", steps);
 #define NIC_HZ_FWD(S1)                                                                                                          \
     do {                                                                                                                        \
         if (e) {                                                                                                                \
             if (int r = allow_lds(horizon_fwd_kernel<8, S1, true>, bytes, who)) return r;                                       \
-            hipLaunchKernelGGL((horizon_fwd_kernel<8, S1, true>), grid, block, bytes, s, HzArgs<true>{*d, *e}, z1_obs, state0,   \
+            hipLaunchKernelGGL((horizon_fwd_kernel<8, S1, true>), grid, block, bytes, s, hz_ensemble_args(d, e, in), z1_obs, state0, \
                                rewards, state_final, state_hist, h1_hist, h2_hist, logits_hist, orders_hist);                   \
         } else {                                                                                                                \
             if (int r = allow_lds(horizon_fwd_kernel<8, S1>, bytes, who)) return r;                                             \
@@ -893,7 +916,7 @@ int launch_fwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsembl
     return nic::check_launch(who);
 }
 
-int launch_bwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsemble* e, const float* state_hist, const float* h1_hist,
+int launch_bwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* in, const float* state_hist, const float* h1_hist,
                const float* h2_hist, const float* logits_hist, const float* orders_hist, NicTable2 g_reward, float* dz1_hist,
                float* dz2_hist, float* dz3_hist, void* stream) {
     if (int r = validate(d, who)) return r;
@@ -905,6 +928,8 @@ int launch_bwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsembl
     if (e) {
         const int why = nic::horizon_ensemble_check_bwd(*d, *e, nic::horizon_ensemble_slices(*d));
         NIC_REQUIRE(why == 0, "%s: %s (%d models)", who, nic::horizon_ensemble_reason(why), e->n_models);
+        const int why_in = in ? nic::horizon_instances_check(*in, e->n_models, *d) : 0;
+        NIC_REQUIRE(why_in == 0, "%s: %s (%d models, %d instances)", who, nic::horizon_instances_reason(why_in), e->n_models, in->n_instances);
     }
     const NicEnvDims& D = d->io.dims;
     const int FD = D.n_stores * D.store_slots + D.n_warehouses * D.warehouse_slots;
@@ -913,13 +938,14 @@ int launch_bwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsembl
     const dim3 grid(nic::ceil_div(D.n_scenarios, NB), e ? e->n_models : 1), block(kThreads);
     hipStream_t s = nic::as_stream(stream);
     const int var = bwd_variant(FD, d->n_out);
-    if (e) nic::note_kernelf("horizon_bwd_kernel<8,%d,models=%d>", var, e->n_models);
+    if (e && in) nic::note_kernelf("horizon_bwd_kernel<8,%d,models=%d,instances=%d>", var, e->n_models, in->n_instances);
+    else if (e) nic::note_kernelf("horizon_bwd_kernel<8,%d,models=%d>", var, e->n_models);
     else nic::note_kernelf("horizon_bwd_kernel<8,%d>", var);
 #define NIC_HZ_BWD(V)                                                                                                           \
     do {                                                                                                                        \
         if (e) {                                                                                                                \
             if (int r = allow_lds(horizon_bwd_kernel<8, V, true>, bytes, who)) return r;                                        \
-            hipLaunchKernelGGL((horizon_bwd_kernel<8, V, true>), grid, block, bytes, s, HzArgs<true>{*d, *e}, state_hist, h1_hist, \
+            hipLaunchKernelGGL((horizon_bwd_kernel<8, V, true>), grid, block, bytes, s, hz_ensemble_args(d, e, in), state_hist, h1_hist, \
                                h2_hist, logits_hist, orders_hist, g_reward, dz1_hist, dz2_hist, dz3_hist);                      \
         } else {                                                                                                                \
             if (int r = allow_lds(horizon_bwd_kernel<8, V>, bytes, who)) return r;                                              \
@@ -953,14 +979,14 @@ int nic_horizon_rollout_ok(const NicHorizonDesc* d) {
 int nic_horizon_rollout_fwd(const NicHorizonDesc* d, const float* z1_obs, const float* state0, float* rewards, float* state_final,
                             float* state_hist, float* h1_hist, float* h2_hist, float* logits_hist, float* orders_hist,
                             void* stream) {
-    return launch_fwd("nic_horizon_rollout_fwd", d, nullptr, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist,
+    return launch_fwd("nic_horizon_rollout_fwd", d, nullptr, nullptr, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist,
                       logits_hist, orders_hist, stream);
 }
 
 int nic_horizon_rollout_bwd(const NicHorizonDesc* d, const float* state_hist, const float* h1_hist, const float* h2_hist,
                             const float* logits_hist, const float* orders_hist, NicTable2 g_reward, float* dz1_hist,
                             float* dz2_hist, float* dz3_hist, void* stream) {
-    return launch_bwd("nic_horizon_rollout_bwd", d, nullptr, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward, dz1_hist,
+    return launch_bwd("nic_horizon_rollout_bwd", d, nullptr, nullptr, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward, dz1_hist,
                       dz2_hist, dz3_hist, stream);
 }
 
@@ -976,7 +1002,7 @@ int nic_horizon_rollout_ensemble_fwd(const NicHorizonDesc* d, const NicHorizonEn
                                      float* rewards, float* state_final, float* state_hist, float* h1_hist, float* h2_hist,
                                      float* logits_hist, float* orders_hist, void* stream) {
     NIC_REQUIRE(e != nullptr, "nic_horizon_rollout_ensemble_fwd: null ensemble");
-    return launch_fwd("nic_horizon_rollout_ensemble_fwd", d, e, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist,
+    return launch_fwd("nic_horizon_rollout_ensemble_fwd", d, e, nullptr, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist,
                       logits_hist, orders_hist, stream);
 }
 
@@ -984,7 +1010,25 @@ int nic_horizon_rollout_ensemble_bwd(const NicHorizonDesc* d, const NicHorizonEn
                                      const float* h2_hist, const float* logits_hist, const float* orders_hist, NicTable2 g_reward,
                                      float* dz1_hist, float* dz2_hist, float* dz3_hist, void* stream) {
     NIC_REQUIRE(e != nullptr, "nic_horizon_rollout_ensemble_bwd: null ensemble");
-    return launch_bwd("nic_horizon_rollout_ensemble_bwd", d, e, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward, dz1_hist,
+    return launch_bwd("nic_horizon_rollout_ensemble_bwd", d, e, nullptr, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward, dz1_hist,
                       dz2_hist, dz3_hist, stream);
+}
+
+/* ---- K models on I problem instances (csrc/horizon_ensemble_plan.h: the model -> instance rule, the offsets and the checks) ---- */
+int nic_horizon_rollout_instances_fwd(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* inst,
+                                      const float* z1_obs, const float* state0, float* rewards, float* state_final, float* state_hist,
+                                      float* h1_hist, float* h2_hist, float* logits_hist, float* orders_hist, void* stream) {
+    NIC_REQUIRE(e != nullptr && inst != nullptr, "nic_horizon_rollout_instances_fwd: null ensemble / instances");
+    return launch_fwd("nic_horizon_rollout_instances_fwd", d, e, inst, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist,
+                      logits_hist, orders_hist, stream);
+}
+
+int nic_horizon_rollout_instances_bwd(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* inst,
+                                      const float* state_hist, const float* h1_hist, const float* h2_hist, const float* logits_hist,
+                                      const float* orders_hist, NicTable2 g_reward, float* dz1_hist, float* dz2_hist, float* dz3_hist,
+                                      void* stream) {
+    NIC_REQUIRE(e != nullptr && inst != nullptr, "nic_horizon_rollout_instances_bwd: null ensemble / instances");
+    return launch_bwd("nic_horizon_rollout_instances_bwd", d, e, inst, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward,
+                      dz1_hist, dz2_hist, dz3_hist, stream);
 }
 }

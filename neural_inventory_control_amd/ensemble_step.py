@@ -9,11 +9,14 @@ weights before it launches (bound: nothing; bind requested: bind on the first ba
 `train_step` around an engine's `_step`, and the epoch loop `fit` / `load_best` with the best weights per model kept on the device.
 An engine provides `_step`, `run` and `train_step` with its own signatures, and sizes `grad` / `_grad_views` with its buffers.
 `check_model_list` is the part of the engines' `check_models` that does not depend on the policy."""
+import copy
+
 import torch
 
 from . import _lib
 from . import small_rollout as sr
 from .ensemble_adam import EnsembleAdam
+from .layout import EnvProblem, Table
 from .rollout import FusedRollout
 
 MAX_MODELS = 65535   # (grid y = model)
@@ -79,6 +82,56 @@ def check_model_list(models, who, policies, handles, arch, mismatch, own=None, v
         if versus_first is not None:
             versus_first(i, m, models[0])
     return models
+
+
+# ---- I problem instances under one launch pair (the engines stage a list of batches with these) -------------------------------------
+def check_instances(probs, n_models, trace_lengths=None, who="SmallPolicyEnsemble"):
+    """The problem instances one launch pair takes: I >= 1 `EnvProblem`s, I dividing the K models, that agree in everything the
+    kernels take once - B, the pipeline shape, the flags, the trace length (`trace_lengths`, one per instance, if given) and every
+    table's layout (present or not, uniform or per-scenario: one descriptor addresses all instances).  ValueError names the first
+    mismatch; `who`: the engine the messages name.  Host-side only.  Returns the replicas per instance."""
+    probs = list(probs)
+    I = len(probs)
+    if I < 1:
+        raise ValueError(f"{who} needs at least one problem instance")
+    if n_models % I != 0:
+        raise ValueError(f"{who}: {I} problem instances do not divide {n_models} models")
+    first = probs[0]
+    for i, p in enumerate(probs[1:], 1):
+        if p.B != first.B:
+            raise ValueError(f"instance {i}: {p.B} scenarios, instance 0 has {first.B}")
+        if trace_lengths is not None and trace_lengths[i] != trace_lengths[0]:
+            raise ValueError(f"instance {i}: a demand trace of {trace_lengths[i]} periods, instance 0's has {trace_lengths[0]}")
+        shape = lambda q: (q.S, q.Wn, q.E, q.Ws, q.Ww, q.We)  # noqa: E731
+        if shape(p) != shape(first):
+            raise ValueError(f"instance {i}: pipeline shape (S, Wn, E, Ws, Ww, We) = {shape(p)} differs from instance 0's {shape(first)}")
+        if (p.lost_demand, p.maximize_profit) != (first.lost_demand, first.maximize_profit):
+            raise ValueError(f"instance {i}: lost_demand / maximize_profit differ from instance 0's")
+        for name in EnvProblem._TABLES:
+            a, b = getattr(first, name), getattr(p, name)
+            if (a.tensor is None) != (b.tensor is None):
+                raise ValueError(f"instance {i}: table {name!r} is {'missing' if b.tensor is None else 'present'}, instance 0's is not")
+            if a.tensor is not None and (a.scn_stride == 0) != (b.scn_stride == 0):
+                kind = lambda t: "uniform" if t.scn_stride == 0 else "per-scenario"  # noqa: E731
+                raise ValueError(f"instance {i}: table {name!r} is {kind(b)}, instance 0's is {kind(a)}")
+            if a.tensor is not None and ((tuple(a.tensor.shape), a.loc_stride, a.sup_stride)
+                                         != (tuple(b.tensor.shape), b.loc_stride, b.sup_stride)):
+                raise ValueError(f"instance {i}: table {name!r} has shape {tuple(b.tensor.shape)}, instance 0's {tuple(a.tensor.shape)}")
+    return n_models // I
+
+
+def stack_instance_tables(probs):
+    """An `EnvProblem` like probs[0] whose tables are [I][...] stacks of the instances' (instance 0 first: a descriptor built from it
+    points at instance 0, instance i's copy of a table starts i x the returned stride behind) and {table: stride in floats}."""
+    stacked, strides = copy.copy(probs[0]), {}
+    for name in EnvProblem._TABLES:
+        t = getattr(probs[0], name)
+        if t.tensor is None:
+            continue
+        tensor = torch.stack([getattr(p, name).tensor.contiguous() for p in probs])
+        setattr(stacked, name, Table(tensor, t.loc_stride, t.scn_stride, t.sup_stride))
+        strides[name] = tensor[0].numel()
+    return stacked, strides
 
 
 class EnsembleStep:

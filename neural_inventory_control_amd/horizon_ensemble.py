@@ -29,8 +29,20 @@ packed with one `torch.cat` per run unless the parameters are bound), gradients 
 inputs `X [K][F][T][ldb]` (the kernel writes model m's state rows into X[m]; the observation rows are model-independent, filled once
 and copied), `z1_obs [K][H1][T][ldb]`, costs `rewards [K][T][ldb]`, histories and pre-activation gradients `[K][rows][T][ldb]`.
 
-Not part of this engine: graph replay, problem instances per model, Trainer / YAML / `main_run` wiring, a `torch.library` operator,
-multi-GPU sharding, bf16 GEMMs.
+The K models need not share the batch: `run`, `train_step` and `fit` take a list (or tuple) of I batch dicts in place of one, I
+dividing K, and model m then runs on instance m // (K // I) - its own demand trace, initial state and cost / lead-time tables
+(`nic_horizon_rollout_instances_*`: the same launch pair, every model reading its instance's inputs).  That is a sweep of the
+underage cost, the lead times or the 72-product slice of a real-data setting, times seeds, in one engine.  The instances share the
+topology (the adjacency mask is `problem_params`'), B, the trace length, the pipeline shape (lead times may differ within it), the
+flags, the policy's input row count and `period_shift`; `check_instances` names the first mismatch.  The engine owns the
+instance-stacked inputs per batch shape (`inst_demand [I][T_total][S][ldb]`, `inst_state0 [I][F_dyn][ldb]`, one stacked tensor per
+table); the observation rows are filled once per instance into X[i * R] and copied to its other R - 1 replicas, and the
+observation GEMM reads every model's own rows (`X_stride` = one model's slice; its plan is model 0's either way, so no bit of a
+model's result depends on which form ran).  The weight-gradient GEMMs, the reductions and the optimizer do not know about
+instances.  A plain dict is the one-batch path and calls `nic_horizon_rollout_ensemble_*` as before.
+
+Not part of this engine: graph replay, per-instance topology / B / horizon, Trainer / YAML / `main_run` wiring, a `torch.library`
+operator, multi-GPU sharding, bf16 GEMMs.
 """
 import types
 
@@ -39,9 +51,10 @@ import torch
 from . import _lib, ops
 from . import horizon_rollout as hz
 from . import small_rollout as sr
+from .ensemble_step import check_instances as _check_problems
 from .ensemble_step import (check_model_list, EnsembleStep, grad_views, layer_slices,  # noqa: F401  (the last two: re-exports)
-                            packed_count, pack_ensemble_weights)
-from .layout import demand_trace_soa, Table
+                            packed_count, pack_ensemble_weights, stack_instance_tables)
+from .layout import demand_trace_soa, EnvProblem, Table
 from .rollout import _pad32, FusedRollout
 
 
@@ -58,6 +71,34 @@ def check_models(models):
                             _layer_sizes, "layer sizes {} differ from model 0's {}")
 
 
+def input_rows(prob, data, observation_params):
+    """rows of the policy's input for a batch (neural_networks.py:452-470): the state, then the past-demand window, the two cost rows per
+    store, the time features and the lead times"""
+    FD = prob.S * prob.Ws + prob.Wn * prob.Ww
+    return (FD + prob.S * observation_params["demand"]["past_periods"] + 2 * prob.S + data["days_from_christmas"].shape[1]
+            + prob.S * data["lead_times"].shape[2])
+
+
+def check_instances(probs, n_models, datas, observation_params):
+    """The problem instances one launch pair takes: I >= 1 batches (their `EnvProblem`s and dicts), I dividing the K models, that
+    agree in what the kernels and the GEMMs take once - B, the trace length, the pipeline shape, the flags, every table's presence,
+    layout and shape (`ensemble_step.check_instances`), the policy's input row count (past-demand window, time features) and
+    `period_shift`.  `observation_params`: one dict for all instances, or one per instance.  ValueError names the first mismatch.
+    Host-side only.  Returns the replicas per instance."""
+    R = _check_problems(probs, n_models, [int(d["demands"].shape[2]) for d in datas], who="HorizonPolicyEnsemble")
+    obs = list(observation_params) if isinstance(observation_params, (list, tuple)) else [observation_params] * len(probs)
+    if len(obs) != len(probs):
+        raise ValueError(f"HorizonPolicyEnsemble: {len(obs)} observation_params for {len(probs)} problem instances")
+    rows = [input_rows(p, d, o) for p, d, o in zip(probs, datas, obs)]
+    for i in range(1, len(probs)):
+        if rows[i] != rows[0]:
+            raise ValueError(f"instance {i}: the policy's input has {rows[i]} rows (past-demand window, time features), instance 0's {rows[0]}")
+        if obs[i]["demand"]["period_shift"] != obs[0]["demand"]["period_shift"]:
+            raise ValueError(f"instance {i}: period_shift {obs[i]['demand']['period_shift']} differs from instance 0's "
+                             f"{obs[0]['demand']['period_shift']}")
+    return R
+
+
 class HorizonPolicyEnsemble(EnsembleStep):
     def __init__(self, models, problem_params, device):
         super().__init__(check_models(models), problem_params, device)
@@ -65,13 +106,16 @@ class HorizonPolicyEnsemble(EnsembleStep):
         self.plan = self.prob = None
         self.model_gemms = True         # one GEMM launch for all K models where the library takes the shape; False: the per-model loop
 
-    def _setup(self, prob, T, train, dims, shift):
+    def _setup(self, prob, T, train, dims, shift, instances=()):
+        """`instances`: what the key of a list-of-instances batch carries besides the shape (I, the trace length, the tables'
+        layouts); a one-batch run has none."""
         K, dev, ld = self.n_models, self.device, prob.ldb
         z = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
-        key = (prob.B, T, K, tuple(dims), prob.S, prob.Wn, prob.Ws, prob.Ww, shift)
+        key = (prob.B, T, K, tuple(dims), prob.S, prob.Wn, prob.Ws, prob.Ww, shift) + tuple(instances)
         if self._key != key:
             self._key = None
-            for name in ("X", "z1", "W1obs", "hist", "dz", "slabs", "rewards", "final", "state0", "scratch", "totals"):
+            for name in ("X", "z1", "W1obs", "hist", "dz", "slabs", "rewards", "final", "state0", "scratch", "totals",
+                         "inst_demand", "inst_state0", "inst_prob", "inst", "inst_sources"):
                 setattr(self, name, None)   # release the previous shape's buffers before sizing the new ones
             F, FD = dims[0], prob.S * prob.Ws + prob.Wn * prob.Ww
             if not hz.HorizonPlan.supports(prob, "data_driven", dims) or not hz.offsets_ok(prob, T, T + shift, hz.MAX_HIDDEN):
@@ -135,60 +179,125 @@ class HorizonPolicyEnsemble(EnsembleStep):
     # ---- one batch ---------------------------------------------------------------------------------------------------------------
     def run(self, data, periods, ignore_periods=0, train=True, observation_params=None, grad_scale=None, accumulate_grads=False,
             discrete_allocation=False):
-        """Rollout of one batch under every model (and, if `train`, d(mean loss)/d(theta) into every model's `param.grad`: views
-        into one [K][P] gradient buffer, `accumulate_grads` adds - `small_rollout.assign_grads`).  Arguments as `FusedRollout.run`.
+        """Rollout of one batch - or, `data` a list of I batches, of instance m // (K // I)'s batch - under every model (and, if
+        `train`, d(mean loss)/d(theta) into every model's `param.grad`: views into one [K][P] gradient buffer, `accumulate_grads`
+        adds - `small_rollout.assign_grads`).  Arguments as `FusedRollout.run`.
         Returns (total [K], reported [K]) device tensors; `rewards` [K][T][ldb] holds the per-period costs.  A setting the
         whole-horizon kernels do not take is a ValueError: there is no fall-back to K single steps."""
         return self._run((data, periods, ignore_periods, observation_params, grad_scale), train, accumulate_grads, discrete_allocation)
 
     def train_step(self, data, periods, ignore_periods=0, optimizer=None, observation_params=None, grad_scale=None):
-        """One whole training step of all K models: forward, the cost reduction, backward, the batched weight gradients and
-        `optimizer.step(self.weights, self.grad)` (an `EnsembleAdam` over this engine's (K, P)) - no packing, no `param.grad`, no
+        """One whole training step of all K models (on one batch, or on a list of I instances' batches as in `run`): forward, the
+        cost reduction, backward, the batched weight gradients and `optimizer.step(self.weights, self.grad)` (an `EnsembleAdam`
+        over this engine's (K, P)) - no packing, no `param.grad`, no
         per-model Python.  Needs `bind_parameters()`.  Returns (total [K], reported [K]) of the step BEFORE the update, as `run`
         does."""
         return self._train_step((data, periods, ignore_periods, observation_params, grad_scale), optimizer)
 
+    def _stage_instances(self, datas, probs, T_total):
+        """A list of I batches: the instances' traces, initial states and tables into this batch shape's stacked buffers (the tables
+        only when the batches present other tensors than last time).  Returns (the problem, demand trace and initial state the
+        descriptor points at - instance 0's, instance i's i x a stride behind) and the NicHorizonInstances."""
+        prob0, dev, I = probs[0], self.device, len(probs)
+        B, ld, FD = prob0.B, prob0.ldb, self.F_dyn
+        if self.inst_state0 is None:
+            self.inst_state0 = torch.zeros(I, FD, ld, device=dev)
+            self.inst_demand = torch.zeros(I, T_total, prob0.S, ld, device=dev)
+            self.inst_prob, table_strides = stack_instance_tables(probs)
+            self.inst_sources = probs
+            self.inst = hz.instance_strides(I, state0=FD * ld, demand=T_total * prob0.S * ld, **table_strides)
+        elif not all(a is b for a, b in zip(self.inst_sources, probs)):
+            for name in EnvProblem._TABLES:   # (other batches than last time: their tables into the stacked ones, in place)
+                stacked = getattr(self.inst_prob, name).tensor
+                if stacked is not None:
+                    for i, p in enumerate(probs):
+                        stacked[i].copy_(getattr(p, name).tensor)
+            self.inst_sources = probs
+        for i, data in enumerate(datas):
+            self.inst_demand[i, :, :, :B].copy_(data["demands"].permute(2, 1, 0))
+            self._fill_state0(self.inst_state0[i], prob0, data)
+        return (self.inst_prob, self.inst_demand, self.inst_state0), self.inst
+
+    @staticmethod
+    def _fill_state0(state0, prob, data):
+        """state0 [F_dyn][ldb] <- the batch's initial pipelines: stores, then warehouses (the reference's cat order)"""
+        a, B = prob.S * prob.Ws, prob.B
+        state0[:a].view(prob.S, prob.Ws, -1)[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
+        if prob.Wn:
+            state0[a:].view(prob.Wn, prob.Ww, -1)[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
+
     def _step(self, data, periods, ignore_periods, observation_params, grad_scale, train, discrete_allocation, optimizer):
+        """`data` a dict: all K models on one batch (`nic_horizon_rollout_ensemble_*`); a list or tuple of I dicts: model m on its
+        instance's (`nic_horizon_rollout_instances_*`, also for I = 1).  The kind of input decides the staging and the launch pair's
+        entry points; the rest is one path."""
         lead, dev, K = self._engines[0], self.device, self.n_models
-        if not FusedRollout.observation_ok(self.models[0], observation_params, data):
-            raise ValueError("data_driven needs a past-demand window and the days_from_christmas time feature")
-        prob = self.prob = lead._problem_for(data)
+        listed = isinstance(data, (list, tuple))
+        if listed:
+            datas = list(data)
+            I = len(datas)
+            if I < 1 or K % I != 0:   # (before anything is built from the batches)
+                raise ValueError(f"HorizonPolicyEnsemble: {I} problem instances do not divide {K} models")
+            obs = list(observation_params) if isinstance(observation_params, (list, tuple)) else [observation_params] * I
+            if len(obs) != I:
+                raise ValueError(f"HorizonPolicyEnsemble: {len(obs)} observation_params for {I} problem instances")
+            for d, o in zip(datas, obs):
+                if not FusedRollout.observation_ok(self.models[0], o, d):
+                    raise ValueError("data_driven needs a past-demand window and the days_from_christmas time feature")
+            probs = [lead._problem_for(d) for d in datas]
+            R = check_instances(probs, K, datas, obs)
+            observation_params = obs[0]
+        else:   # (one batch: nothing to compare, no per-instance Python)
+            if not FusedRollout.observation_ok(self.models[0], observation_params, data):
+                raise ValueError("data_driven needs a past-demand window and the days_from_christmas time feature")
+            datas, probs, obs, I, R = (data,), (lead._problem_for(data),), (observation_params,), 1, K
+        prob = self.prob = probs[0]
         T, B, ld = periods, prob.B, prob.ldb
         shift = observation_params["demand"]["period_shift"]
-        P_ = observation_params["demand"]["past_periods"]
         FD = prob.S * prob.Ws + prob.Wn * prob.Ww
-        F = FD + prob.S * P_ + 2 * prob.S + data["days_from_christmas"].shape[1] + prob.S * data["lead_times"].shape[2]
+        F = input_rows(prob, datas[0], observation_params)
         lins, dims = self._layers(F)
         if self._bound and dims[0] != F:
             raise ValueError(f"HorizonPolicyEnsemble: this batch gives the policy {F} input rows, the bound parameters have {dims[0]}")
         if prob.E != 0 or len(dims) != 4:
             raise ValueError(f"HorizonPolicyEnsemble: the whole-horizon kernels do not take this setting / policy (layer sizes {dims}, "
                              f"{prob.E} extra echelons)")
-        demand_soa = demand_trace_soa(data["demands"], ld, dev)
-        if demand_soa.shape[0] < T + shift:
+        T_total = int(datas[0]["demands"].shape[2])
+        if T_total < T + shift:
             raise ValueError("Current period is greater than the number of periods in the data")
-        self._setup(prob, T, train, dims, shift)
+        if listed:
+            layouts = tuple((name, getattr(prob, name).scn_stride) for name in EnvProblem._TABLES if getattr(prob, name).tensor is not None)
+            self._setup(prob, T, train, dims, shift, instances=("instances", I, T_total, layouts))
+        else:
+            self._setup(prob, T, train, dims, shift)
         self._ready_weights(lins, dims, optimizer)
         Fo, n_cols = F - FD, T * ld
         batched = self.model_gemms and self._models_ok
         P, sl = self.weights.shape[1], layer_slices(dims)
-        a = prob.S * prob.Ws
-        self.state0[:a].view(prob.S, prob.Ws, ld)[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
-        if prob.Wn:
-            self.state0[a:].view(prob.Wn, prob.Ww, ld)[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
-        # the observation rows are the same for every model: filled once (FusedRollout's own routine), copied to the other K - 1
+        if listed:
+            (prob_d, demand_soa, state0), inst = self._stage_instances(datas, probs, T_total)
+            traces = demand_soa
+        else:
+            prob_d, demand_soa, state0, inst = prob, demand_trace_soa(data["demands"], ld, dev), self.state0, None
+            traces = demand_soa.unsqueeze(0)
+            self._fill_state0(state0, prob, data)
+        # the observation rows do not depend on the model: filled once per instance (FusedRollout's own routine) into its first
+        # replica's block, then one copy to every instance's other R - 1
         X = self.X
         lead.F, lead.F_dyn = F, FD   # (what the routine reads of its engine besides the window scratch it keeps: the row counts)
-        lead._fill_observation_rows(X[0].transpose(0, 1), data, prob, T, shift, observation_params, demand_soa)
-        if K > 1:
-            X[1:, FD:].copy_(X[0, FD:].unsqueeze(0).expand(K - 1, Fo, T, ld))
+        for i, (d, p, o) in enumerate(zip(datas, probs, obs)):
+            lead._fill_observation_rows(X[i * R].transpose(0, 1), d, p, T, shift, o, traces[i])
+        if R > 1:
+            Xi = X.view(I, R, F, T, ld)
+            Xi[:, 1:, FD:].copy_(Xi[:, :1, FD:].expand(I, R - 1, Fo, T, ld))
         # with the single-model route's operands: the observation rows' share of the first layer for every period (+ bias)
         row0 = self.weights[0]
         if batched:
-            # one strided copy and one launch: the weights and biases are read in the packed rows, the observation rows are shared
+            # one strided copy and one launch: the weights and biases are read in the packed rows; the observation rows are shared
+            # (one batch: X stride 0) or every model's own block's (a list of instances: X stride = one model's slice of X)
             o, n, k, bo = sl[0]
             self.W1obs[:, :, :Fo].copy_(self.weights[:, o:o + n * k].view(K, n, k)[:, :, FD:])
-            ops.linear_fwd_models(self.W1obs[:, :, :Fo], row0[bo:bo + n], X[0, FD:].view(Fo, n_cols), self.z1.view(K, dims[1], n_cols),
+            x_obs = X[:, FD:].flatten(2) if listed else X[0, FD:].view(Fo, n_cols)
+            ops.linear_fwd_models(self.W1obs[:, :, :Fo], row0[bo:bo + n], x_obs, self.z1.view(K, dims[1], n_cols),
                                   n_cols, _lib.NIC_ACT_NONE, bias_stride=P)
         else:
             for m, ls in enumerate(lins or [eng._linears() for eng in self._engines]):
@@ -198,7 +307,7 @@ class HorizonPolicyEnsemble(EnsembleStep):
         self._note("z1")
         # the descriptor points at model 0's row of the packed weights
         views = [types.SimpleNamespace(weight=row0[o:o + n * k].view(n, k), bias=row0[bo:bo + n]) for o, n, k, bo in sl]
-        desc = self.plan.desc(prob, T, shift, views, self.edge_mask, demand_soa, n_cols, round_orders=discrete_allocation)
+        desc = self.plan.desc(prob_d, T, shift, views, self.edge_mask, demand_soa, n_cols, round_orders=discrete_allocation)
         if not self._checked:   # once per shape: the library's own limits
             if not hz.horizon_ok(desc):
                 msg = _lib.lib().nic_last_error()
@@ -206,7 +315,11 @@ class HorizonPolicyEnsemble(EnsembleStep):
             self._checked = True
         ens = self._ensemble(desc, train)
         hist = ([X] + self.hist) if train else [None] * 5
-        hz.horizon_ensemble_fwd(desc, ens, self.z1, self.state0, self.rewards, self.final, *hist)
+        if inst is None:
+            fwd, bwd, where = hz.horizon_ensemble_fwd, hz.horizon_ensemble_bwd, (desc, ens)
+        else:
+            fwd, bwd, where = hz.horizon_instances_fwd, hz.horizon_instances_bwd, (desc, ens, inst)
+        fwd(*where, self.z1, state0, self.rewards, self.final, *hist)
         self._note("fwd")
         # every model's total / reported cost: one fixed-order reduction (two launches) for all K
         sr.small_rollout_ensemble_reduce(self._reduce, None, 0, 0, 0, None, self.rewards, n_cols, ignore_periods * ld, self.totals,
@@ -217,7 +330,7 @@ class HorizonPolicyEnsemble(EnsembleStep):
         if grad_scale is None:
             grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
         self._g_reward_key = sr.set_g_reward(self.g_reward, B, grad_scale, self._g_reward_key)
-        hz.horizon_ensemble_bwd(desc, ens, *hist, Table(self.g_reward, 0, 1), *self.dz)
+        bwd(*where, *hist, Table(self.g_reward, 0, 1), *self.dz)
         self._note("bwd")
         # three weight gradients per model: FusedRollout._wgrad_over_columns' launches on model m's slices
         if batched:

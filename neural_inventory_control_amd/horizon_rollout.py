@@ -113,3 +113,36 @@ def horizon_ensemble_bwd(desc, ens, state_hist, h1_hist, h2_hist, logits_hist, o
     _lib.check(_lib.lib().nic_horizon_rollout_ensemble_bwd(desc, ens, p(state_hist), p(h1_hist), p(h2_hist), p(logits_hist),
                                                            p(orders_hist), g_reward.t2(), p(dz1), p(dz2), p(dz3),
                                                            _lib.current_stream()))
+
+
+# ---- K models on I problem instances (nic_horizon_rollout_instances_*, csrc/horizon_ensemble_plan.h) --------------------------------
+INSTANCE_FIELDS = _lib.HORIZON_INSTANCE_FIELDS
+
+
+def instance_strides(n_instances, **strides):
+    """NicHorizonInstances: floats between two instances' demand traces, initial states and tables (what is not named: 0, shared)."""
+    inst = _lib.NicHorizonInstances()
+    inst.n_instances = int(n_instances)
+    for k, v in strides.items():
+        if k not in INSTANCE_FIELDS:
+            raise KeyError(k)
+        setattr(inst, k, int(v))
+    return inst
+
+
+def horizon_instances_fwd(desc, ens, inst, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist, logits_hist, orders_hist):
+    """`horizon_ensemble_fwd` with model m on instance m // (ens.n_models // inst.n_instances): `desc` (demand, tables) and `state0`
+    are instance 0's, instance i's start i x its stride behind."""
+    ops._dev(rewards)
+    p = _lib.ptr
+    _lib.check(_lib.lib().nic_horizon_rollout_instances_fwd(desc, ens, inst, p(z1_obs), p(state0), p(rewards), p(state_final), p(state_hist),
+                                                            p(h1_hist), p(h2_hist), p(logits_hist), p(orders_hist),
+                                                            _lib.current_stream()))
+
+
+def horizon_instances_bwd(desc, ens, inst, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward: Table, dz1, dz2, dz3):
+    ops._dev(dz1)
+    p = _lib.ptr
+    _lib.check(_lib.lib().nic_horizon_rollout_instances_bwd(desc, ens, inst, p(state_hist), p(h1_hist), p(h2_hist), p(logits_hist),
+                                                            p(orders_hist), g_reward.t2(), p(dz1), p(dz2), p(dz3),
+                                                            _lib.current_stream()))

@@ -30,12 +30,11 @@ and their launch replay, the staging and the launches.
 
 YAML / `main_run` wiring, a `torch.library` operator and multi-GPU sharding are not part of this engine.
 """
-import copy
-
 import torch
 
 from . import small_rollout as sr
-from .ensemble_step import check_model_list, EnsembleStep, grad_views, pack_ensemble_weights  # noqa: F401  (the last: a re-export)
+from .ensemble_step import (check_instances, check_model_list, EnsembleStep, grad_views,  # noqa: F401
+                            pack_ensemble_weights, stack_instance_tables)   # (`check_instances`, `pack_ensemble_weights`: re-exports)
 from .launch_replay import LaunchReplay, ReplayedEngine
 from .layout import demand_trace_soa, EnvProblem, Table
 from .rollout import _HEADS, FusedRollout  # noqa: F401  (`FusedRollout`: a re-export)
@@ -70,55 +69,6 @@ def check_models(models):
     Host-side only; the setting's side of `SmallRolloutPlan.supports` is checked when the first batch arrives."""
     return check_model_list(models, "SmallPolicyEnsemble", SMALL_POLICIES, f"the ELU MLP policies {SMALL_POLICIES}", _arch,
                             "architecture {} differs from model 0's {}", _hidden_rule, _upper_bound_rule)
-
-
-def check_instances(probs, n_models, trace_lengths=None):
-    """The problem instances one launch pair takes: I >= 1 `EnvProblem`s, I dividing the K models, that agree in everything the
-    kernels take once - B, the pipeline shape, the flags, the trace length (`trace_lengths`, one per instance, if given) and every
-    table's layout (present or not, uniform or per-scenario: one descriptor addresses all instances).  ValueError names the first
-    mismatch.  Host-side only.  Returns the replicas per instance."""
-    probs = list(probs)
-    I = len(probs)
-    if I < 1:
-        raise ValueError("SmallPolicyEnsemble needs at least one problem instance")
-    if n_models % I != 0:
-        raise ValueError(f"SmallPolicyEnsemble: {I} problem instances do not divide {n_models} models")
-    first = probs[0]
-    for i, p in enumerate(probs[1:], 1):
-        if p.B != first.B:
-            raise ValueError(f"instance {i}: {p.B} scenarios, instance 0 has {first.B}")
-        if trace_lengths is not None and trace_lengths[i] != trace_lengths[0]:
-            raise ValueError(f"instance {i}: a demand trace of {trace_lengths[i]} periods, instance 0's has {trace_lengths[0]}")
-        shape = lambda q: (q.S, q.Wn, q.E, q.Ws, q.Ww, q.We)  # noqa: E731
-        if shape(p) != shape(first):
-            raise ValueError(f"instance {i}: pipeline shape (S, Wn, E, Ws, Ww, We) = {shape(p)} differs from instance 0's {shape(first)}")
-        if (p.lost_demand, p.maximize_profit) != (first.lost_demand, first.maximize_profit):
-            raise ValueError(f"instance {i}: lost_demand / maximize_profit differ from instance 0's")
-        for name in EnvProblem._TABLES:
-            a, b = getattr(first, name), getattr(p, name)
-            if (a.tensor is None) != (b.tensor is None):
-                raise ValueError(f"instance {i}: table {name!r} is {'missing' if b.tensor is None else 'present'}, instance 0's is not")
-            if a.tensor is not None and (a.scn_stride == 0) != (b.scn_stride == 0):
-                kind = lambda t: "uniform" if t.scn_stride == 0 else "per-scenario"  # noqa: E731
-                raise ValueError(f"instance {i}: table {name!r} is {kind(b)}, instance 0's is {kind(a)}")
-            if a.tensor is not None and ((tuple(a.tensor.shape), a.loc_stride, a.sup_stride)
-                                         != (tuple(b.tensor.shape), b.loc_stride, b.sup_stride)):
-                raise ValueError(f"instance {i}: table {name!r} has shape {tuple(b.tensor.shape)}, instance 0's {tuple(a.tensor.shape)}")
-    return n_models // I
-
-
-def stack_instance_tables(probs):
-    """An `EnvProblem` like probs[0] whose tables are [I][...] stacks of the instances' (instance 0 first: a descriptor built from it
-    points at instance 0, instance i's copy of a table starts i x the returned stride behind) and {table: stride in floats}."""
-    stacked, strides = copy.copy(probs[0]), {}
-    for name in EnvProblem._TABLES:
-        t = getattr(probs[0], name)
-        if t.tensor is None:
-            continue
-        tensor = torch.stack([getattr(p, name).tensor.contiguous() for p in probs])
-        setattr(stacked, name, Table(tensor, t.loc_stride, t.scn_stride, t.sup_stride))
-        strides[name] = tensor[0].numel()
-    return stacked, strides
 
 
 class _ShapeState:
