@@ -3,8 +3,8 @@
 The packed-row layout: `weights [K][P]`, row m = model m's layers in `nn.Linear`'s own order (per layer the weight, row-major, then
 the bias) - `layer_slices`, `packed_count`, `grad_views`, `pack_ensemble_weights`, all on `dims = [F, H1, ..., n_out]`.
 
-`EnsembleStep`, the engines' base: the borrowed single-model engines (problem cache and LazyLinear materialisation are theirs),
-materialising and comparing the models' layers, `weights` and binding the models' parameters to its rows, what a step does with the
+`EnsembleStep`, the engines' base: the one problem cache of the ensemble, materialising (policy_layers.py, in model order) and
+comparing the models' layers, `weights` and binding the models' parameters to its rows, what a step does with the
 weights before it launches (bound: nothing; bind requested: bind on the first batch; else pack, every run), the frames of `run` and
 `train_step` around an engine's `_step`, and the epoch loop `fit` / `load_best` with the best weights per model kept on the device.
 An engine provides `_step`, `run` and `train_step` with its own signatures, and sizes `grad` / `_grad_views` with its buffers.
@@ -16,8 +16,8 @@ import torch
 from . import _lib
 from . import small_rollout as sr
 from .ensemble_adam import EnsembleAdam
-from .layout import EnvProblem, Table
-from .rollout import FusedRollout
+from .layout import EnvProblem, ProblemCache, Table
+from .policy_layers import materialize_linears, materialized_linears, supports
 
 MAX_MODELS = 65535   # (grid y = model)
 
@@ -71,7 +71,7 @@ def check_model_list(models, who, policies, handles, arch, mismatch, own=None, v
         raise ValueError(f"{who} takes at most 65,535 models")
     for i, m in enumerate(models):
         name = getattr(m, "nn_args", {}).get("name") if hasattr(m, "nn_args") else None
-        if name not in policies or not FusedRollout.supports(m):
+        if name not in policies or not supports(m):
             raise ValueError(f"model {i}: {who} handles {handles}, got {name!r}")
         if own is not None:
             own(i, m)
@@ -85,17 +85,23 @@ def check_model_list(models, who, policies, handles, arch, mismatch, own=None, v
 
 
 # ---- I problem instances under one launch pair (the engines stage a list of batches with these) -------------------------------------
+def instance_replicas(n_instances, n_models, who):
+    """models per problem instance; the instances must divide the K models (needs the batches' count only: the engines ask before
+    anything is built from the batches)"""
+    if n_instances < 1 or n_models % n_instances != 0:
+        raise ValueError(f"{who}: {n_instances} problem instances do not divide {n_models} models")
+    return n_models // n_instances
+
+
 def check_instances(probs, n_models, trace_lengths=None, who="SmallPolicyEnsemble"):
     """The problem instances one launch pair takes: I >= 1 `EnvProblem`s, I dividing the K models, that agree in everything the
     kernels take once - B, the pipeline shape, the flags, the trace length (`trace_lengths`, one per instance, if given) and every
     table's layout (present or not, uniform or per-scenario: one descriptor addresses all instances).  ValueError names the first
     mismatch; `who`: the engine the messages name.  Host-side only.  Returns the replicas per instance."""
     probs = list(probs)
-    I = len(probs)
-    if I < 1:
+    if len(probs) < 1:
         raise ValueError(f"{who} needs at least one problem instance")
-    if n_models % I != 0:
-        raise ValueError(f"{who}: {I} problem instances do not divide {n_models} models")
+    replicas = instance_replicas(len(probs), n_models, who)
     first = probs[0]
     for i, p in enumerate(probs[1:], 1):
         if p.B != first.B:
@@ -117,7 +123,7 @@ def check_instances(probs, n_models, trace_lengths=None, who="SmallPolicyEnsembl
             if a.tensor is not None and ((tuple(a.tensor.shape), a.loc_stride, a.sup_stride)
                                          != (tuple(b.tensor.shape), b.loc_stride, b.sup_stride)):
                 raise ValueError(f"instance {i}: table {name!r} has shape {tuple(b.tensor.shape)}, instance 0's {tuple(a.tensor.shape)}")
-    return n_models // I
+    return replicas
 
 
 def stack_instance_tables(probs):
@@ -134,14 +140,30 @@ def stack_instance_tables(probs):
     return stacked, strides
 
 
+def refresh_instance_tables(stacked, sources, probs):
+    """The instances' tables into `stacked`'s (what `stack_instance_tables` made of `sources`), in place, if `probs` are other
+    batches' problems than `sources` (the problem cache hands the same object out for the same tensors).  Returns the sources now."""
+    if all(a is b for a, b in zip(sources, probs)):
+        return sources
+    for name in EnvProblem._TABLES:
+        tensor = getattr(stacked, name).tensor
+        if tensor is not None:
+            for i, p in enumerate(probs):
+                tensor[i].copy_(getattr(p, name).tensor)
+    return probs
+
+
+def table_layouts(prob):
+    """what a list-of-instances batch adds to a batch shape's key for its tables: (table, scenario stride) of those present"""
+    return tuple((name, getattr(prob, name).scn_stride) for name in EnvProblem._TABLES if getattr(prob, name).tensor is not None)
+
+
 class EnsembleStep:
     def __init__(self, models, problem_params, device):
         """`models`: what the engine's `check_models` returned"""
         _lib.require_device()
         self.models, self.problem_params, self.device = models, problem_params, torch.device(device)
-        # (one single-model engine per model: problem cache, LazyLinear materialisation, the upper bound and the observation rows
-        # are theirs; they allocate nothing until they run, and they never run here)
-        self._engines = [FusedRollout(m, problem_params, device) for m in models]
+        self._problems = ProblemCache()   # (one for the ensemble: the same tensors presented again give the same `EnvProblem` object)
         self.last_kernels = {}          # launch class -> kernel name the library recorded in the last run
         self.weights = self.grad = self._grad_views = None   # [K][P], [K][>= P]: once per engine
         self.param_shapes = None        # shapes of one model's parameters in `parameters()` order (EnsembleAdam's `param_shapes`)
@@ -160,14 +182,22 @@ class EnsembleStep:
     # ---- the models' layers and the rows of `weights` -------------------------------------------------------------------------------------
     def _materialize(self, F):
         """(every model's layers, their common sizes [F, H1, ..., n_out]), LazyLinear first layers materialised for F inputs"""
-        for eng in self._engines:
-            eng.materialize(F)
-        lins = [eng._linears() for eng in self._engines]
+        for m in self.models:
+            materialize_linears(m.master_linears(), F)
+        lins = self._linears()
         dims = [[ls[0].in_features] + [m.out_features for m in ls] for ls in lins]
         for i, d in enumerate(dims):
             if d != dims[0]:
                 raise ValueError(f"model {i}: layer sizes {d} differ from model 0's {dims[0]}")
         return lins, dims[0]
+
+    def _linears(self):
+        """every model's materialised layers"""
+        return [materialized_linears(m) for m in self.models]
+
+    def _problem_for(self, data):
+        """EnvProblem of a batch (cached per presented tensors, see layout.ProblemCache)"""
+        return self._problems.get(self.problem_params, data, self.device)
 
     def _layers(self, F):
         """(layers, sizes) a step on F input rows runs with; bound: (None, the bound sizes) - nothing is packed, and the per-model
@@ -221,8 +251,8 @@ class EnsembleStep:
     def param_grads(self):
         """[(parameter, gradient view into the [K][P] buffer of the last training run)] over all models"""
         out = []
-        for eng, (gw, gb) in zip(self._engines, self._grad_views):
-            for i, m in enumerate(eng._linears()):
+        for lins, (gw, gb) in zip(self._linears(), self._grad_views):
+            for i, m in enumerate(lins):
                 out += [(m.weight, gw[i]), (m.bias, gb[i])]
         return out
 

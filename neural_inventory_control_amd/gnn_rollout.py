@@ -20,8 +20,9 @@ import torch
 
 from . import _lib, ops
 from .launch_replay import LaunchReplay, ReplayedEngine
-from .layout import demand_trace_soa, free_hbm, ProblemCache, Table
+from .layout import demand_trace_soa, fill_initial_state, free_hbm, ProblemCache, Table
 from .ops import EnvState, Mlp3Segment
+from .policy_layers import materialize_linears
 
 MODULES = ("initial_node", "initial_edge", "node_update", "edge_update", "output")
 
@@ -275,10 +276,8 @@ class GnnRollout(ReplayedEngine):
 
     def materialize(self, Dn):
         """Creates the lazy first layers without a forward pass (same default init as the reference's first call)."""
-        from .rollout import FusedRollout
         for name, k in zip(MODULES, (Dn, 65, 96, 96, 32)):
-            shim = type("S", (), {"master_linears": lambda s, n=name: self._linears(n)})()
-            FusedRollout.materialize(type("E", (), {"model": shim})(), k)
+            materialize_linears(self._linears(name), k)
 
     def _setup(self, prob, data, T, train):
         key = (prob.B, T, bool(train), prob.S, prob.Wn, prob.Ws, prob.Ww, self.fused_bwd, self.keep_inputs,
@@ -452,9 +451,7 @@ class GnnRollout(ReplayedEngine):
             self._pdesc, self._bdesc = {}, {}   # (... and so do the cached launch descriptors)
         P.lead[0, :P.n_int].copy_(data["lead_times"][0][P.lead_store, P.lead_wh])
         P.lead[0, P.n_int:P.n_int + P.Wn].copy_(data["warehouse_lead_times"][0, :P.Wn])
-        s0 = self._views(self.states[0], prob)
-        s0.store[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
-        s0.wh[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
+        fill_initial_state(self.states[0], prob, data)
         # static node features (rows max_inv..): warehouses [holding, (edge cost)], stores [holding, underage, mean, std]
         f, mi, Wn = self.feat, self.max_inv, P.Wn
         f[:, mi, :Wn, :B] = data["warehouse_holding_costs"].t()

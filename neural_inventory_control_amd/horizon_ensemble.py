@@ -7,7 +7,7 @@ workgroups: a serial chain of 95 periods on 2 % of the device.  Seeds, learning 
 the idle CUs instead of paying K steps.  Every model runs the instruction stream of the single-model kernels on its own slice of
 the buffers, and the four GEMMs around the launch pair (the observation rows' share of the first layer, three weight gradients)
 run with the operands, shapes, strides and split counts `FusedRollout`'s whole-horizon route uses - so each model's costs,
-final state and gradients are the bits `FusedRollout(model).run` gives for it (trainer.py:181-216 once per model).  The totals are
+final state and gradients are the bits `FusedRollout.run` gives for that model alone (trainer.py:181-216 once per model).  The totals are
 one fixed-order reduction for all K models (the cost half of `nic_small_rollout_ensemble_reduce`): they agree with the single-model
 `torch.sum` to rounding, not to the bit.
 
@@ -21,8 +21,9 @@ single-model calls instead (4 K GEMM launches + 6 K around them).
 `train_step`: after `bind_parameters()` every model's `weight` / `bias` are views of its row of `weights [K][P]`, nothing is packed,
 and an `EnsembleAdam(K, P)` updates all K rows with two launches - no per-model Python.  `fit` is the epoch loop over `train_step`
 with the best weights per model kept on the device.  Packing, binding, the frames of `run` / `train_step`, `fit` and the generic
-model checks are `EnsembleStep`'s (ensemble_step.py, shared with `SmallPolicyEnsemble`); this module has the policy's rules, the
-buffers of a batch shape and the launches.
+model checks are `EnsembleStep`'s (ensemble_step.py, shared with `SmallPolicyEnsemble`), model and batch preparation are the
+functions every engine calls (policy_layers.py, layout.py: no single-model engine is built here); this module has the policy's
+rules, the buffers of a batch shape and the launches.
 
 Layout: weights `[K][P]` in `nn.Linear`'s own order (ensemble_step.py's packed row: per layer the weight, row-major, then the bias;
 packed with one `torch.cat` per run unless the parameters are bound), gradients `[K][P]` in the same order (`param.grad` are views of it),
@@ -52,10 +53,12 @@ from . import _lib, ops
 from . import horizon_rollout as hz
 from . import small_rollout as sr
 from .ensemble_step import check_instances as _check_problems
-from .ensemble_step import (check_model_list, EnsembleStep, grad_views, layer_slices,  # noqa: F401  (the last two: re-exports)
-                            packed_count, pack_ensemble_weights, stack_instance_tables)
-from .layout import demand_trace_soa, EnvProblem, Table
-from .rollout import _pad32, FusedRollout
+from .ensemble_step import (check_model_list, EnsembleStep, grad_views, instance_replicas, layer_slices,
+                            refresh_instance_tables, stack_instance_tables, table_layouts)
+from .ensemble_step import packed_count, pack_ensemble_weights  # noqa: F401  (re-exports)
+from .layout import data_driven_input_rows, demand_trace_soa, edge_mask, fill_initial_state, fill_observation_rows, Table
+from .policy_layers import observation_ok
+from .rollout import _pad32, FusedRollout  # noqa: F401  (`FusedRollout`: a re-export)
 
 
 def _layer_sizes(model):
@@ -72,11 +75,16 @@ def check_models(models):
 
 
 def input_rows(prob, data, observation_params):
-    """rows of the policy's input for a batch (neural_networks.py:452-470): the state, then the past-demand window, the two cost rows per
-    store, the time features and the lead times"""
-    FD = prob.S * prob.Ws + prob.Wn * prob.Ww
-    return (FD + prob.S * observation_params["demand"]["past_periods"] + 2 * prob.S + data["days_from_christmas"].shape[1]
-            + prob.S * data["lead_times"].shape[2])
+    """rows of the policy's input for a batch: the state (stores, then warehouses), then the observation rows"""
+    return data_driven_input_rows(prob.S * prob.Ws + prob.Wn * prob.Ww, data, observation_params)
+
+
+def _per_instance(observation_params, n_instances):
+    """one observation_params per instance, from one dict for all instances or a list of one per instance"""
+    obs = list(observation_params) if isinstance(observation_params, (list, tuple)) else [observation_params] * n_instances
+    if len(obs) != n_instances:
+        raise ValueError(f"HorizonPolicyEnsemble: {len(obs)} observation_params for {n_instances} problem instances")
+    return obs
 
 
 def check_instances(probs, n_models, datas, observation_params):
@@ -86,9 +94,7 @@ def check_instances(probs, n_models, datas, observation_params):
     `period_shift`.  `observation_params`: one dict for all instances, or one per instance.  ValueError names the first mismatch.
     Host-side only.  Returns the replicas per instance."""
     R = _check_problems(probs, n_models, [int(d["demands"].shape[2]) for d in datas], who="HorizonPolicyEnsemble")
-    obs = list(observation_params) if isinstance(observation_params, (list, tuple)) else [observation_params] * len(probs)
-    if len(obs) != len(probs):
-        raise ValueError(f"HorizonPolicyEnsemble: {len(obs)} observation_params for {len(probs)} problem instances")
+    obs = _per_instance(observation_params, len(probs))
     rows = [input_rows(p, d, o) for p, d, o in zip(probs, datas, obs)]
     for i in range(1, len(probs)):
         if rows[i] != rows[0]:
@@ -104,6 +110,7 @@ class HorizonPolicyEnsemble(EnsembleStep):
         super().__init__(check_models(models), problem_params, device)
         self._key = None
         self.plan = self.prob = None
+        self._dpad = None               # `fill_observation_rows`' window scratch
         self.model_gemms = True         # one GEMM launch for all K models where the library takes the shape; False: the per-model loop
 
     def _setup(self, prob, T, train, dims, shift, instances=()):
@@ -129,11 +136,7 @@ class HorizonPolicyEnsemble(EnsembleStep):
             self.X = z(K, F, T, ld)       # rows [0, FD): state before period t (written by the kernel); then the observation rows
             self.z1 = z(K, dims[1], T, ld)
             self.W1obs = z(K, dims[1], _pad32(F - FD))   # (rows padded to 32 floats, as FusedRollout's: the GEMM's A-tile loads are float4)
-            if prob.Wn:
-                conn = self.problem_params["warehouse_store_adjacency"]
-                self.edge_mask = torch.tensor(conn, dtype=torch.float32, device=dev).t().contiguous()   # [S][Wn]
-            else:
-                self.edge_mask = None
+            self.edge_mask = edge_mask(self.problem_params, dev)
             self.totals = z(K, 2)
             n_scratch = sr.small_rollout_reduce_scratch(0, 0, T * ld)
             self.scratch = torch.empty(K, n_scratch, device=dev)
@@ -206,50 +209,34 @@ class HorizonPolicyEnsemble(EnsembleStep):
             self.inst_prob, table_strides = stack_instance_tables(probs)
             self.inst_sources = probs
             self.inst = hz.instance_strides(I, state0=FD * ld, demand=T_total * prob0.S * ld, **table_strides)
-        elif not all(a is b for a, b in zip(self.inst_sources, probs)):
-            for name in EnvProblem._TABLES:   # (other batches than last time: their tables into the stacked ones, in place)
-                stacked = getattr(self.inst_prob, name).tensor
-                if stacked is not None:
-                    for i, p in enumerate(probs):
-                        stacked[i].copy_(getattr(p, name).tensor)
-            self.inst_sources = probs
+        else:   # (other batches than last time: their tables into the stacked ones, in place)
+            self.inst_sources = refresh_instance_tables(self.inst_prob, self.inst_sources, probs)
         for i, data in enumerate(datas):
             self.inst_demand[i, :, :, :B].copy_(data["demands"].permute(2, 1, 0))
-            self._fill_state0(self.inst_state0[i], prob0, data)
+            fill_initial_state(self.inst_state0[i], prob0, data)
         return (self.inst_prob, self.inst_demand, self.inst_state0), self.inst
-
-    @staticmethod
-    def _fill_state0(state0, prob, data):
-        """state0 [F_dyn][ldb] <- the batch's initial pipelines: stores, then warehouses (the reference's cat order)"""
-        a, B = prob.S * prob.Ws, prob.B
-        state0[:a].view(prob.S, prob.Ws, -1)[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
-        if prob.Wn:
-            state0[a:].view(prob.Wn, prob.Ww, -1)[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
 
     def _step(self, data, periods, ignore_periods, observation_params, grad_scale, train, discrete_allocation, optimizer):
         """`data` a dict: all K models on one batch (`nic_horizon_rollout_ensemble_*`); a list or tuple of I dicts: model m on its
         instance's (`nic_horizon_rollout_instances_*`, also for I = 1).  The kind of input decides the staging and the launch pair's
         entry points; the rest is one path."""
-        lead, dev, K = self._engines[0], self.device, self.n_models
+        dev, K = self.device, self.n_models
         listed = isinstance(data, (list, tuple))
         if listed:
             datas = list(data)
             I = len(datas)
-            if I < 1 or K % I != 0:   # (before anything is built from the batches)
-                raise ValueError(f"HorizonPolicyEnsemble: {I} problem instances do not divide {K} models")
-            obs = list(observation_params) if isinstance(observation_params, (list, tuple)) else [observation_params] * I
-            if len(obs) != I:
-                raise ValueError(f"HorizonPolicyEnsemble: {len(obs)} observation_params for {I} problem instances")
+            instance_replicas(I, K, "HorizonPolicyEnsemble")   # (this and the next: before anything is built from the batches)
+            obs = _per_instance(observation_params, I)
             for d, o in zip(datas, obs):
-                if not FusedRollout.observation_ok(self.models[0], o, d):
+                if not observation_ok(self.models[0], o, d):
                     raise ValueError("data_driven needs a past-demand window and the days_from_christmas time feature")
-            probs = [lead._problem_for(d) for d in datas]
+            probs = [self._problem_for(d) for d in datas]
             R = check_instances(probs, K, datas, obs)
             observation_params = obs[0]
         else:   # (one batch: nothing to compare, no per-instance Python)
-            if not FusedRollout.observation_ok(self.models[0], observation_params, data):
+            if not observation_ok(self.models[0], observation_params, data):
                 raise ValueError("data_driven needs a past-demand window and the days_from_christmas time feature")
-            datas, probs, obs, I, R = (data,), (lead._problem_for(data),), (observation_params,), 1, K
+            datas, probs, obs, I, R = (data,), (self._problem_for(data),), (observation_params,), 1, K
         prob = self.prob = probs[0]
         T, B, ld = periods, prob.B, prob.ldb
         shift = observation_params["demand"]["period_shift"]
@@ -265,8 +252,7 @@ class HorizonPolicyEnsemble(EnsembleStep):
         if T_total < T + shift:
             raise ValueError("Current period is greater than the number of periods in the data")
         if listed:
-            layouts = tuple((name, getattr(prob, name).scn_stride) for name in EnvProblem._TABLES if getattr(prob, name).tensor is not None)
-            self._setup(prob, T, train, dims, shift, instances=("instances", I, T_total, layouts))
+            self._setup(prob, T, train, dims, shift, instances=("instances", I, T_total, table_layouts(prob)))
         else:
             self._setup(prob, T, train, dims, shift)
         self._ready_weights(lins, dims, optimizer)
@@ -279,13 +265,17 @@ class HorizonPolicyEnsemble(EnsembleStep):
         else:
             prob_d, demand_soa, state0, inst = prob, demand_trace_soa(data["demands"], ld, dev), self.state0, None
             traces = demand_soa.unsqueeze(0)
-            self._fill_state0(state0, prob, data)
-        # the observation rows do not depend on the model: filled once per instance (FusedRollout's own routine) into its first
+            fill_initial_state(state0, prob, data)
+        # the observation rows do not depend on the model: filled once per instance (the routine `FusedRollout` uses) into its first
         # replica's block, then one copy to every instance's other R - 1
         X = self.X
-        lead.F, lead.F_dyn = F, FD   # (what the routine reads of its engine besides the window scratch it keeps: the row counts)
         for i, (d, p, o) in enumerate(zip(datas, probs, obs)):
-            lead._fill_observation_rows(X[i * R].transpose(0, 1), d, p, T, shift, o, traces[i])
+            P_ = o["demand"]["past_periods"]
+            shape = (P_ + traces[i].shape[0], p.S, p.ldb)
+            if self._dpad is None or self._dpad.shape != shape:
+                self._dpad = torch.zeros(shape, device=dev)
+            end = fill_observation_rows(X[i * R].transpose(0, 1), FD, p.S, P_, T, p.B, shift, d, traces[i], self._dpad)
+            assert end == F
         if R > 1:
             Xi = X.view(I, R, F, T, ld)
             Xi[:, 1:, FD:].copy_(Xi[:, :1, FD:].expand(I, R - 1, Fo, T, ld))
@@ -300,7 +290,7 @@ class HorizonPolicyEnsemble(EnsembleStep):
             ops.linear_fwd_models(self.W1obs[:, :, :Fo], row0[bo:bo + n], x_obs, self.z1.view(K, dims[1], n_cols),
                                   n_cols, _lib.NIC_ACT_NONE, bias_stride=P)
         else:
-            for m, ls in enumerate(lins or [eng._linears() for eng in self._engines]):
+            for m, ls in enumerate(lins or self._linears()):
                 self.W1obs[m, :, :Fo].copy_(ls[0].weight.detach()[:, FD:])
                 ops.linear_fwd(self.W1obs[m, :, :Fo], ls[0].bias.detach(), X[m, FD:].view(Fo, n_cols), self.z1[m].view(dims[1], n_cols),
                                n_cols, _lib.NIC_ACT_NONE)

@@ -65,6 +65,36 @@ def free_hbm(device):
     return torch.cuda.mem_get_info(device)[0] + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
 
 
+def fill_initial_state(block, prob, data, stores_only=False, changed=None):
+    """block [rows][ldb] <- the batch's initial pipelines in the reference's cat(flatten(...)) order: row s * Ws + j, column b =
+    initial_inventories[b, s, j], then the warehouses' and the extra echelons' the same way; columns [B, ldb) are left alone.
+    `stores_only`: the store rows only (the softplus head's input).  `changed(slot, dst, src)`: the caller's say, per part
+    ("store" / "wh" / "ech", the [n][W][B] view to fill, the batch's tensor), whether it is copied; None copies every part."""
+    parts = [("store", "initial_inventories", prob.S, prob.Ws), ("wh", "initial_warehouse_inventories", prob.Wn, prob.Ww),
+             ("ech", "initial_echelon_inventories", prob.E, prob.We)]
+    o = 0
+    for slot, key, n, w in parts[:1] if stores_only else parts:
+        if n:   # (a part the setting does not have costs no view: this runs in every step of the launch-bound routes)
+            dst = block[o:o + n * w].view(n, w, -1)[:, :, :prob.B]
+            if changed is None or changed(slot, dst, data[key]):
+                dst.copy_(data[key].permute(1, 2, 0))
+        o += n * w
+
+
+def edge_mask(problem_params, device):
+    """[S][Wn] float32, 1 where `warehouse_store_adjacency` ([Wn][S]) joins the pair; None in a setting without warehouses"""
+    if not int(problem_params["n_warehouses"]):
+        return None
+    return torch.tensor(problem_params["warehouse_store_adjacency"], dtype=torch.float32, device=device).t().contiguous()
+
+
+def data_driven_input_rows(state_rows, data, observation_params):
+    """rows of the data_driven policy's input for a batch (neural_networks.py:452-470): the `state_rows` pipeline rows, then what
+    `fill_observation_rows` puts behind them - the past-demand window, two cost rows per store, the time features, the lead times"""
+    S, W = data["lead_times"].shape[1:]
+    return state_rows + S * observation_params["demand"]["past_periods"] + 2 * S + data["days_from_christmas"].shape[1] + S * W
+
+
 def fill_observation_rows(X, f_dyn, S, P, T, B, shift, data, demand_soa, dpad):
     """data_driven: the observation rows behind the `f_dyn` state rows of every period's input block, in the reference's
     concatenation order (neural_networks.py:452-470): past demands [S][P] (the window demands[t+shift-P : t+shift], zeros to

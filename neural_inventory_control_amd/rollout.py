@@ -22,15 +22,14 @@ from collections import namedtuple
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, policy_layers
 from . import horizon_rollout as hz
 from . import small_rollout as sr
 from .launch_replay import LaunchReplay, ReplayedEngine
-from .layout import demand_trace_soa, fill_observation_rows, free_hbm, EnvProblem, ProblemCache, Table
+from .layout import (data_driven_input_rows, demand_trace_soa, edge_mask, fill_initial_state, fill_observation_rows, free_hbm,
+                     EnvProblem, ProblemCache, Table)
 from .ops import EnvState
-
-_HEADS = {"vanilla_one_store": "softplus", "vanilla_warehouse": "warehouse", "vanilla_serial": "serial",
-          "data_driven": "data_driven"}
+from .policy_layers import HEADS as _HEADS
 
 
 GEMM_PRECISIONS = ("fp32", "bf16")
@@ -107,34 +106,8 @@ _Ctx = namedtuple("_Ctx", "prob T B ld shift train Wv Wtv biases L demand")
 
 
 class FusedRollout(ReplayedEngine):
-    @staticmethod
-    def supports(model):
-        name = getattr(model, "nn_args", {}).get("name") if hasattr(model, "nn_args") else None
-        if name not in _HEADS or type(model).__name__ not in ("VanillaOneStore", "VanillaWarehouse", "VanillaSerial",
-                                                              "DataDrivenNet"):
-            return False
-        a = model.nn_args
-        if name == "data_driven":   # the real-data policy (data_driven_net.yml): ELU inside, ReLU on the output layer
-            return (type(model).__name__ == "DataDrivenNet" and a["inner_layer_activations"]["master"] == "elu"
-                    and a["output_layer_activation"]["master"] == "relu" and len(a["neurons_per_hidden_layer"]["master"]) >= 1)
-        return (type(model).__name__ != "DataDrivenNet" and a["inner_layer_activations"]["master"] == "elu"
-                and a["output_layer_activation"]["master"] is None and len(a["neurons_per_hidden_layer"]["master"]) >= 1)
-
-    @staticmethod
-    def observation_ok(model, observation_params, data=None):
-        """Can this engine build the policy's observation?  The vanilla policies read the inventories only (no past-demand
-        window, no time / sample features: trainer.py's generic loop otherwise); data_driven reads the past-demand window and
-        `days_from_christmas` (neural_networks.py:452-470) and nothing else that moves with the period."""
-        op = observation_params
-        if op is None:
-            return False
-        past, tf, sf = (op["demand"] or {}).get("past_periods"), op["time_features"], op["sample_features"]
-        past = past if isinstance(past, int) else 0   # (`past_periods: null` / a missing key: no window -> the generic route)
-        if getattr(model, "nn_args", {}).get("name") == "data_driven":
-            # (sample features, e.g. `store_nbr`, may be in the observation: DataDrivenNet.forward does not read them)
-            return (isinstance(tf, (list, tuple)) and list(tf) == ["days_from_christmas"] and past >= 1
-                    and (data is None or ("days_from_christmas" in data and "underage_costs" in data)))
-        return past == 0 and not tf and not sf
+    supports = staticmethod(policy_layers.supports)
+    observation_ok = staticmethod(policy_layers.observation_ok)   # (model, observation_params, data=None)
 
     def __init__(self, model, problem_params, device):
         _lib.require_device()
@@ -192,12 +165,12 @@ class FusedRollout(ReplayedEngine):
         self.eval_history = None  # evaluation keeps per-period states/orders/logits: None = while small, True / False = forced
         self.small = None       # SmallRolloutPlan when the current shapes take that route
         self._prob_cache = ProblemCache()
-        self.inputs_versioned = False   # (opt-in, see _copy_if_changed)
+        self.inputs_versioned = False   # (opt-in, see _input_changed)
         self._copied = {}
         self._shift_hint = 0
         self._wide_shapes = self._wide_bwd = False
         self._tail_slots = 0
-        self._ub_cache = (None, None)
+        self._ub_cache = {}
         self._dpad = self._thin = self._hz_checked = self.sr_scratch = self._g_reward_key = None
 
     def _k(self, tag, fn, *args, **kw):
@@ -226,33 +199,11 @@ class FusedRollout(ReplayedEngine):
 
     # ---- buffers ------------------------------------------------------------------------------------------------
     def _linears(self):
-        lins = self.model.master_linears()
-        if any(isinstance(m.weight, torch.nn.parameter.UninitializedParameter) for m in lins):
-            raise RuntimeError("policy has un-materialised LazyLinear layers; call materialize() or run one forward")
-        return lins
+        return policy_layers.materialized_linears(self.model)
 
     def materialize(self, in_features):
         """Materialises LazyLinear layers without a forward pass (same default init as the reference's first call)."""
-        k = in_features
-        for m in self.model.master_linears():
-            fresh = isinstance(m.weight, torch.nn.parameter.UninitializedParameter)
-            if fresh:
-                m.in_features = k
-                m.weight.materialize((m.out_features, k))
-                if m.bias is not None:
-                    m.bias.materialize((m.out_features,))
-                m.reset_parameters()
-            elif hasattr(m, "cls_to_become") and m.cls_to_become is not None:
-                # a lazy layer whose parameters came from load_state_dict (checkpoint loaded into a fresh model): the
-                # tensors exist, but the module still reports in_features = 0 and is still the lazy class
-                m.in_features = m.weight.shape[1]
-            if fresh or (hasattr(m, "cls_to_become") and m.cls_to_become is not None):
-                for hook in ("_initialize_hook", "_load_hook"):  # what LazyModuleMixin._infer_parameters does
-                    if hasattr(m, hook):
-                        getattr(m, hook).remove()
-                        delattr(m, hook)
-                m.__class__ = m.cls_to_become
-            k = m.out_features
+        policy_layers.materialize_linears(self.model.master_linears(), in_features)
 
     def _setup(self, prob, T, train, extra_rows=0):
         key = (prob.B, T, bool(train), prob.S, prob.Wn, prob.E, prob.Ws, prob.Ww, prob.We, self.batch_wgrad, self.use_thin,
@@ -341,11 +292,7 @@ class FusedRollout(ReplayedEngine):
             self.hz_X = z(F, T, ld)               # rows [0, FD): state before period t (written by the kernel); then the observation rows
             self.hz_z1 = z(dims[1], T, ld)
             self.hz_W1obs = z(dims[1], _pad32(Fo))   # (rows padded to 32 floats: the GEMM's A-tile loads are float4)
-            if prob.Wn:
-                conn = self.problem_params["warehouse_store_adjacency"]
-                self.edge_mask = torch.tensor(conn, dtype=torch.float32, device=dev).t().contiguous()   # [S][Wn]
-            else:
-                self.edge_mask = None
+            self.edge_mask = edge_mask(self.problem_params, dev)
             if train:
                 self.hz_hist = [z(dims[1], T, ld), z(dims[2], T, ld), z(dims[3], T, ld), z(plan.n_ord + prob.Wn, T, ld)]  # h1, h2, logits, orders (+ shipped)
                 self.hz_dz = [z(dims[i + 1], T, ld) for i in range(L)]   # (padding columns stay zero: the kernel writes live ones only)
@@ -469,9 +416,8 @@ class FusedRollout(ReplayedEngine):
                 self.gb_c = z(gd[-1]) if lins[-1].bias is not None else None
         if self.head == "warehouse":
             self.adj = self.model.adjacency(prob.S, prob.Wn, dev)
-        if self.head == "data_driven" and prob.Wn:
-            conn = self.problem_params["warehouse_store_adjacency"]
-            self.edge_mask = torch.tensor(conn, dtype=torch.float32, device=dev).t().contiguous()   # [S][Wn]
+        if self.head == "data_driven":
+            self.edge_mask = edge_mask(self.problem_params, dev)
         self._key = key
 
     def _views(self, block, prob):
@@ -494,13 +440,7 @@ class FusedRollout(ReplayedEngine):
 
     def _ub(self):
         """Scalar order upper bound of the policy (read back from the device once, not per call / per capture)."""
-        ub = self.model.warehouse_upper_bound
-        if not torch.is_tensor(ub):
-            return float(ub)
-        key = (ub.data_ptr(), ub._version)
-        if self._ub_cache[0] != key:
-            self._ub_cache = (key, float(ub.reshape(-1)[0]))
-        return self._ub_cache[1]
+        return policy_layers.upper_bound(self.model, self._ub_cache)
 
     # ---- one batch ----------------------------------------------------------------------------------------------
     def run(self, data, periods, ignore_periods=0, train=True, observation_params=None, demand_soa=None,
@@ -520,14 +460,13 @@ class FusedRollout(ReplayedEngine):
         self._round = bool(discrete_allocation)
         self._T_last = periods
         dev = self.device
-        prob = self._problem_for(data)
+        prob = self._prob_cache.get(self.problem_params, data, self.device)   # (cached per presented tensors: layout.ProblemCache)
         T, B, ld = periods, prob.B, prob.ldb
         extra = 0
         if self.head == "data_driven":
             if not self.observation_ok(self.model, observation_params, data):
                 raise ValueError("data_driven needs a past-demand window and the days_from_christmas time feature")
-            P_ = observation_params["demand"]["past_periods"]
-            extra = prob.S * P_ + 2 * prob.S + data["days_from_christmas"].shape[1] + prob.S * data["lead_times"].shape[2]
+            extra = data_driven_input_rows(0, data, observation_params)
         self._shift_hint = observation_params["demand"]["period_shift"] if observation_params else 0
         self._setup(prob, T, train, extra)
         replay = self._replay
@@ -579,12 +518,7 @@ class FusedRollout(ReplayedEngine):
         Wtv = [self.Wt[i][:self.gd[i], :self.gd[i + 1]] for i in range(L)]
 
         # initial state
-        s0 = self._views(self.states[0], prob)
-        s0.store[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
-        if prob.Wn:
-            s0.wh[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
-        if prob.E:
-            s0.ech[:, :, :B].copy_(data["initial_echelon_inventories"].permute(1, 2, 0))
+        fill_initial_state(self.states[0], prob, data)
 
         if self.head == "data_driven":
             self._fill_observation_rows(self.states[:T], data, prob, T, shift, observation_params, demand_soa)
@@ -627,11 +561,7 @@ class FusedRollout(ReplayedEngine):
         rows = n("initial_inventories")
         if self.head != "softplus":
             rows += n("initial_warehouse_inventories") + n("initial_echelon_inventories")
-        if self.head == "data_driven":
-            S = data["initial_inventories"].shape[1]
-            rows += (S * observation_params["demand"]["past_periods"] + 2 * S + data["days_from_christmas"].shape[1]
-                     + S * data["lead_times"].shape[2])
-        return rows
+        return data_driven_input_rows(rows, data, observation_params) if self.head == "data_driven" else rows
 
     def _fill_observation_rows(self, X, data, prob, T, shift, observation_params, demand_soa):
         """data_driven: the observation rows of every period's input block (X: the blocks as a [T][F][ld] view), outside the period
@@ -662,20 +592,19 @@ class FusedRollout(ReplayedEngine):
         tt = self.sr_totals.clone()   # (the caller's tensors must not change under a later step)
         return tt[0], tt[1]
 
-    def _copy_if_changed(self, slot, dst, src):
-        """dst <- src.permute(1, 2, 0); with `inputs_versioned` (opt-in: bench.py, whose batch nobody writes) the copy is skipped
-        when `src` is the very tensor (same object, same in-place version) that was copied into the same destination last time.
+    def _input_changed(self, slot, dst, src):
+        """Must `src` be copied into `dst`?  With `inputs_versioned` (opt-in: bench.py, whose batch nobody writes) not when `src` is
+        the very tensor (same object, same in-place version) that was copied into the same destination last time.
         torch's version counter does not see every write - raw-pointer kernels (the HIP sampler), `.data` assignments, `set_()` -
         so by default every presented batch is copied: one small launch."""
         if not self.inputs_versioned:
-            dst.copy_(src.permute(1, 2, 0))
-            return
+            return True
         key = (dst.data_ptr(), tuple(dst.shape), src._version)
         hit = self._copied.get(slot)
         if hit is not None and hit[0] is src and hit[1] == key:
-            return
-        dst.copy_(src.permute(1, 2, 0))
+            return False
         self._copied[slot] = (src, key)
+        return True
 
     def _set_g_reward(self, B, T, grad_scale):
         """g_reward <- d(loss)/d(reward[b, t]); default 1 / (B * T * S) = trainer.py:169"""
@@ -695,21 +624,12 @@ class FusedRollout(ReplayedEngine):
     def _assign_grads(self, accumulate):
         sr.assign_grads(self.param_grads(), accumulate)
 
-    def _problem_for(self, data):
-        """EnvProblem of a batch (cached per presented tensors, see layout.ProblemCache)."""
-        return self._prob_cache.get(self.problem_params, data, self.device)
-
     # ---- whole-horizon route for the small policies -------------------------------------------------------------------
     def _run_small(self, data, prob, T, B, ld, shift, demand_soa, ignore_periods, train, grad_scale, accumulate_grads,
                    assign_grads=True):
         plan, lins = self.small, self._linears()
         sr.pack_weights(lins, self.sr_weights)
-        s0 = self._views(self.sr_state0, prob)
-        self._copy_if_changed("s0_store", s0.store[:, :, :B], data["initial_inventories"])
-        if prob.Wn:
-            self._copy_if_changed("s0_wh", s0.wh[:, :, :B], data["initial_warehouse_inventories"])
-        if prob.E:
-            self._copy_if_changed("s0_ech", s0.ech[:, :, :B], data["initial_echelon_inventories"])
+        fill_initial_state(self.sr_state0, prob, data, changed=self._input_changed)
         ub = self._ub() if self.head != "softplus" else 0.0
         width = sr.lane_width(self.small_lane_scenarios, train, B)
         if train and not self.small_wgrad_in_kernel:
@@ -756,10 +676,7 @@ class FusedRollout(ReplayedEngine):
         plan, lins = self.horizon, self._linears()
         F, FD, dims = self.F, self.F_dyn, self.dims
         Fo, n_cols = F - FD, T * ld
-        a = self.F_store
-        self.hz_state0[:a].view(prob.S, prob.Ws, ld)[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
-        if prob.Wn:
-            self.hz_state0[a:].view(prob.Wn, prob.Ww, ld)[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
+        fill_initial_state(self.hz_state0, prob, data)
         X = self.hz_X
         self._fill_observation_rows(X.transpose(0, 1), data, prob, T, shift, observation_params, demand_soa)
         # the observation rows' share of the first layer for every period at once (+ bias): independent of the rollout

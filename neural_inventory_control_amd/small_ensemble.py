@@ -5,7 +5,7 @@ evaluated on ONE batch with one forward launch, one backward launch and one redu
 A wavefront of the whole-horizon kernels is one serial chain of T periods, and at the batch sizes these policies are trained
 with (1,024 - 8,192 scenarios) most SIMDs have no wavefront: seeds, learning rates or initialisations of one architecture ride
 in them instead of paying K steps.  Every model runs the instruction stream of the single-model kernels on its own slice of the
-buffers, so its costs and gradients are the bits `FusedRollout(model).run` gives for it (trainer.py:181-216 once per model).
+buffers, so its costs and gradients are the bits `FusedRollout.run` gives for that model alone (trainer.py:181-216 once per model).
 
 `run` alone leaves the optimizer to the caller (K optimizers, or one with K parameter groups, step the models independently) and
 packs all K models' weights again every call.  The whole training step is `train_step`: after `bind_parameters()` every model's
@@ -25,26 +25,24 @@ per table) at fixed addresses, so a replayed step stages and pins nothing.  A pl
 input is only staged differently (`_stage_batch`, `_stage_instances`): from the descriptor on, `_step` is one path.
 
 The packed-row layout, binding, the frames of `run` / `train_step`, `fit` and the generic model checks are `EnsembleStep`'s
-(ensemble_step.py, shared with `HorizonPolicyEnsemble`); this module has the small policies' rules, the batch shapes' buffers
-and their launch replay, the staging and the launches.
+(ensemble_step.py, shared with `HorizonPolicyEnsemble`), model and batch preparation are the functions every engine calls
+(policy_layers.py, layout.py: no single-model engine is built here); this module has the small policies' rules, the batch
+shapes' buffers and their launch replay, the staging and the launches.
 
 YAML / `main_run` wiring, a `torch.library` operator and multi-GPU sharding are not part of this engine.
 """
 import torch
 
 from . import small_rollout as sr
-from .ensemble_step import (check_instances, check_model_list, EnsembleStep, grad_views,  # noqa: F401
-                            pack_ensemble_weights, stack_instance_tables)   # (`check_instances`, `pack_ensemble_weights`: re-exports)
+from .ensemble_step import (check_instances, check_model_list, EnsembleStep, grad_views, instance_replicas,
+                            refresh_instance_tables, stack_instance_tables, table_layouts)
+from .ensemble_step import pack_ensemble_weights  # noqa: F401  (a re-export)
 from .launch_replay import LaunchReplay, ReplayedEngine
-from .layout import demand_trace_soa, EnvProblem, Table
-from .rollout import _HEADS, FusedRollout  # noqa: F401  (`FusedRollout`: a re-export)
+from .layout import demand_trace_soa, fill_initial_state, Table
+from .policy_layers import HEADS, upper_bound
+from .rollout import FusedRollout  # noqa: F401  (a re-export)
 
 SMALL_POLICIES = ("vanilla_one_store", "vanilla_serial")
-
-
-def _upper_bound(model):
-    ub = model.warehouse_upper_bound
-    return float(ub.reshape(-1)[0]) if torch.is_tensor(ub) else float(ub)
 
 
 def _arch(m):
@@ -59,8 +57,8 @@ def _hidden_rule(i, m):
 
 
 def _upper_bound_rule(i, m, first):
-    if _arch(m)[0] == "vanilla_serial" and _upper_bound(m) != _upper_bound(first):
-        raise ValueError(f"model {i}: warehouse_upper_bound {_upper_bound(m)} differs from model 0's {_upper_bound(first)}")
+    if _arch(m)[0] == "vanilla_serial" and upper_bound(m) != upper_bound(first):
+        raise ValueError(f"model {i}: warehouse_upper_bound {upper_bound(m)} differs from model 0's {upper_bound(first)}")
 
 
 def check_models(models):
@@ -94,7 +92,8 @@ _MAX_KEPT_SHAPES = 4   # other batch shapes kept while their launches are replay
 class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
     def __init__(self, models, problem_params, device):
         super().__init__(check_models(models), problem_params, device)   # (`grad` here: [K][P rounded up to 4])
-        self.head = _HEADS[self.models[0].nn_args["name"]]
+        self.head = HEADS[self.models[0].nn_args["name"]]
+        self._ub_cache = {}             # `upper_bound`'s: model 0's bound is read from the device once, not per step
         self.small_lane_scenarios = 0   # 16 or 32 scenarios per wavefront (0: small_rollout.lane_width's rule)
         self._key = None
         self._shape = _ShapeState(False)   # the current batch shape's buffers and LaunchReplay (read as `ens.rewards`, `ens.plan`, ...)
@@ -193,24 +192,12 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
         Returns (total [K], reported [K]) of the step BEFORE the update, as `run` does."""
         return self._train_step((data, periods, ignore_periods, observation_params, demand_soa, grad_scale), optimizer)
 
-    def _fill_state0(self, state0, prob, data):
-        """state0 [F][ldb] <- the batch's initial pipelines in the reference's cat(flatten(...)) order"""
-        B = prob.B
-        a, b = prob.S * prob.Ws, prob.S * prob.Ws + prob.Wn * prob.Ww
-        state0[:a].view(prob.S, prob.Ws, -1)[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
-        if self.head != "softplus":
-            if prob.Wn:
-                state0[a:b].view(prob.Wn, prob.Ww, -1)[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
-            if prob.E:
-                state0[b:b + prob.E * prob.We].view(prob.E, prob.We, -1)[:, :, :B].copy_(
-                    data["initial_echelon_inventories"].permute(1, 2, 0))
-
     # ---- staging: what differs between the two kinds of input.  Each returns (the problem, demand trace and initial state the
     # descriptor points at), the NicSmallInstances or None, and what the input adds to the captures' variant and to their key --------------
     def _stage_batch(self, data, T, shift, train, demand_soa, optimizer):
         """One batch for all K models.  A captured sequence holds raw pointers: it reads the pinned problem's tables and the staged
         demand trace, refreshed in place."""
-        prob = self._engines[0]._problem_for(data)
+        prob = self._problem_for(data)
         if demand_soa is None:
             demand_soa = demand_trace_soa(data["demands"], prob.ldb, self.device)
         if demand_soa.shape[0] < T + shift:
@@ -219,7 +206,7 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
         sh = self._shape
         prob = sh.replay.pin_problem(prob)
         demand_soa = sh.replay.stage_demand(demand_soa)
-        self._fill_state0(sh.state0, prob, data)
+        fill_initial_state(sh.state0, prob, data, stores_only=self.head == "softplus")
         return (prob, demand_soa, sh.state0), None, (), ()
 
     def _stage_instances(self, datas, T, shift, train, demand_soa, optimizer):
@@ -227,10 +214,9 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
         stacked buffers (the tables only when the batches present other tensors than last time), whose addresses a captured
         sequence keeps: nothing is pinned or staged.  A caller's demand_soa is read in place, so its address is part of the
         capture's key."""
-        lead, dev, K, I = self._engines[0], self.device, self.n_models, len(datas)
-        if I < 1 or K % I != 0:   # (before anything is built from the batches)
-            raise ValueError(f"SmallPolicyEnsemble: {I} problem instances do not divide {K} models")
-        probs = [lead._problem_for(data) for data in datas]
+        dev, K, I = self.device, self.n_models, len(datas)
+        instance_replicas(I, K, "SmallPolicyEnsemble")   # (before anything is built from the batches)
+        probs = [self._problem_for(data) for data in datas]
         lengths = [int(data["demands"].shape[2]) for data in datas]
         check_instances(probs, K, lengths)
         prob0 = probs[0]
@@ -240,8 +226,7 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
         if demand_soa is not None and tuple(demand_soa.shape) != (I, T_total, 1, ld):
             raise ValueError(f"SmallPolicyEnsemble: demand_soa of a list of instances must be [I][T_total][1][ldb] = {(I, T_total, 1, ld)}, "
                              f"got {tuple(demand_soa.shape)}")
-        layouts = tuple((name, getattr(prob0, name).scn_stride) for name in EnvProblem._TABLES if getattr(prob0, name).tensor is not None)
-        self._ready_weights(*self._setup(prob0, T, train, instances=("instances", I, T_total, layouts)), optimizer)
+        self._ready_weights(*self._setup(prob0, T, train, instances=("instances", I, T_total, table_layouts(prob0))), optimizer)
         sh = self._shape
         F = sh.plan.F
         if sh.inst_state0 is None:
@@ -249,13 +234,8 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
             sh.inst_prob, table_strides = stack_instance_tables(probs)
             sh.inst_sources = probs
             sh.inst = sr.instance_strides(I, state0=F * ld, demand=T_total * ld, **table_strides)
-        elif not all(a is b for a, b in zip(sh.inst_sources, probs)):
-            for name in EnvProblem._TABLES:   # (other batches than last time: their tables into the stacked ones, in place)
-                stacked = getattr(sh.inst_prob, name).tensor
-                if stacked is not None:
-                    for i, p in enumerate(probs):
-                        stacked[i].copy_(getattr(p, name).tensor)
-            sh.inst_sources = probs
+        else:   # (other batches than last time: their tables into the stacked ones, in place)
+            sh.inst_sources = refresh_instance_tables(sh.inst_prob, sh.inst_sources, probs)
         if demand_soa is None:
             if sh.inst_demand is None:
                 sh.inst_demand = torch.zeros(I, T_total, 1, ld, device=dev)
@@ -263,7 +243,7 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
             for i, data in enumerate(datas):
                 demand_soa[i, :, :, :B].copy_(data["demands"].permute(2, 1, 0))
         for i, data in enumerate(datas):
-            self._fill_state0(sh.inst_state0[i], prob0, data)
+            fill_initial_state(sh.inst_state0[i], prob0, data, stores_only=self.head == "softplus")
         return (sh.inst_prob, demand_soa, sh.inst_state0), sh.inst, (I,), (I, demand_soa.data_ptr())
 
     def _step(self, data, periods, ignore_periods, observation_params, demand_soa, grad_scale, train, discrete_allocation, optimizer):
@@ -276,7 +256,7 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
         (prob, demand_soa, state0), inst, variant, key = stage(data, T, shift, train, demand_soa, optimizer)
         sh, B, ld = self._shape, prob.B, prob.ldb
         replay = sh.replay
-        ub = self._engines[0]._ub() if self.head != "softplus" else 0.0
+        ub = upper_bound(self.models[0], self._ub_cache) if self.head != "softplus" else 0.0
         width = sr.lane_width(self.small_lane_scenarios, train, B)
         desc = sh.plan.desc(T, shift, self.weights, demand_soa, state0, ub, round_orders=discrete_allocation, prob=prob,
                             lane_scenarios=width)

@@ -19,7 +19,7 @@ import torch
 from . import _lib
 from . import horizon_rollout as hz
 from ._lib import NicHorizonDesc
-from .layout import demand_trace_soa, ProblemCache, Table
+from .layout import demand_trace_soa, edge_mask, fill_initial_state, ProblemCache, Table
 
 _QUANTILE = ("TransformedNV", "QuantileNV", "ReturnsNV", "FixedQuantile")
 
@@ -96,11 +96,7 @@ class TapeRollout:
         if train:
             self.state_hist, self.orders_hist, self.dlevel = z(FD, T, ld), z(n_ord + prob.Wn, T, ld), z(prob.S, T, ld)
             self.g_reward = z(ld)
-        if prob.Wn:
-            conn = self.problem_params["warehouse_store_adjacency"]
-            self.edge_mask = torch.tensor(conn, dtype=torch.float32, device=dev).t().contiguous()
-        else:
-            self.edge_mask = None
+        self.edge_mask = edge_mask(self.problem_params, dev)
         self._key = key
 
     # ---- the tapes: every period's decision inputs in one batched pass ---------------------------------------------------
@@ -178,10 +174,7 @@ class TapeRollout:
         self._setup(prob, T, want_grad)
         self.prob = prob
         demand_soa = demand_trace_soa(d, ld, self.device)
-        a = prob.S * prob.Ws
-        self.state0[:a].view(prob.S, prob.Ws, ld)[:, :, :B].copy_(data["initial_inventories"].permute(1, 2, 0))
-        if prob.Wn:
-            self.state0[a:].view(prob.Wn, prob.Ww, ld)[:, :, :B].copy_(data["initial_warehouse_inventories"].permute(1, 2, 0))
+        fill_initial_state(self.state0, prob, data)
         args = (prob, T, shift, ignore_periods, demand_soa, bool(discrete_allocation))
         if self.jit:
             with torch.no_grad():

@@ -16,7 +16,7 @@ from golden_io import Golden
 from neural_inventory_control_amd import _lib, build
 from neural_inventory_control_amd.ensemble_adam import EnsembleAdam
 from neural_inventory_control_amd.neural_networks import NeuralNetworkCreator
-from neural_inventory_control_amd.rollout import FusedRollout
+from neural_inventory_control_amd.policy_layers import materialize_linears
 from neural_inventory_control_amd.trainer import _portable_optimizer_state
 
 ROOT = eac.ROOT
@@ -215,9 +215,7 @@ def _cpu_models(k):
     for i in range(k):
         torch.manual_seed(100 + i)
         m = NeuralNetworkCreator().create_neural_network(_Sc(), copy.deepcopy(c["nn_params"]), device="cpu")
-        eng = FusedRollout.__new__(FusedRollout)
-        eng.model = m
-        eng.materialize(g.params["net.master.0.weight"].shape[1])
+        materialize_linears(m.master_linears(), g.params["net.master.0.weight"].shape[1])
         out.append(m)
     return out
 

@@ -19,6 +19,7 @@ from neural_inventory_control_amd import _lib, ensemble_step as es, small_rollou
 from neural_inventory_control_amd.data_handling import Scenario
 from neural_inventory_control_amd.ensemble_adam import EnsembleAdam
 from neural_inventory_control_amd.neural_networks import NeuralNetworkCreator
+from neural_inventory_control_amd.policy_layers import materialize_linears
 from neural_inventory_control_amd.rollout import FusedRollout
 from neural_inventory_control_amd.small_ensemble import SmallPolicyEnsemble
 
@@ -149,7 +150,7 @@ def _fresh_models():
     for seed in SEEDS:
         torch.manual_seed(seed)
         m = NeuralNetworkCreator().create_neural_network(sc, policy, device=DEV)
-        FusedRollout(m, setting["problem_params"], DEV).materialize(F)
+        materialize_linears(m.master_linears(), F)
         models.append(m)
     return models
 

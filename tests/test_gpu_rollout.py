@@ -20,6 +20,7 @@ from neural_inventory_control_amd.data_handling import DatasetCreator, DeviceBat
 from neural_inventory_control_amd.environment import Simulator
 from neural_inventory_control_amd.loss_functions import PolicyLoss
 from neural_inventory_control_amd.neural_networks import NeuralNetworkCreator
+from neural_inventory_control_amd.policy_layers import materialize_linears
 from neural_inventory_control_amd.rollout import FusedRollout
 from neural_inventory_control_amd.trainer import Trainer
 
@@ -597,7 +598,7 @@ def test_checkpoint_known_answer_through_hip():
                                                  sample_index_for_split=c["dev_samples"])
     model = NeuralNetworkCreator().create_neural_network(sc, c["nn_params"], device=DEV)
     tr, sim = Trainer(device=DEV), Simulator(device=DEV)
-    FusedRollout(model, c["problem_params"], DEV).materialize(4)
+    materialize_linears(model.master_linears(), 4)
     model.load_state_dict({k: v.to(DEV) for k, v in g.params.items()})
     loader = DeviceBatches(dev_ds, c["dev_samples"], device=DEV)
     for fused in (True, False):
@@ -725,7 +726,7 @@ def test_trainer_train_loop_checkpoint_and_test(tmp_path):
     assert {"epoch", "model_state_dict", "optimizer_state_dict", "best_train_loss", "best_dev_loss", "all_train_losses",
             "all_dev_losses", "all_test_losses", "warehouse_upper_bound"} <= set(ck)
     model2 = NeuralNetworkCreator().create_neural_network(sc, policy, device=DEV)
-    FusedRollout(model2, setting["problem_params"], DEV).materialize(4)
+    materialize_linears(model2.master_linears(), 4)
     opt2 = torch.optim.Adam(model2.parameters(), lr=3e-3)
     tr2 = Trainer(device=DEV)
     tr2.load_model(model2, opt2, str(tmp_path / "a" / "b" / "ckpt.pt"))
@@ -739,7 +740,7 @@ def test_trainer_train_loop_checkpoint_and_test(tmp_path):
     after = {}
     for kind, kw in (("fused", {"fused": True}), ("default", {})):
         model3 = NeuralNetworkCreator().create_neural_network(sc, policy, device=DEV)
-        FusedRollout(model3, setting["problem_params"], DEV).materialize(4)
+        materialize_linears(model3.master_linears(), 4)
         opt3 = torch.optim.Adam(model3.parameters(), lr=3e-3, **kw)
         tr3 = Trainer(device=DEV)
         tr3.load_model(model3, opt3, str(tmp_path / "a" / "b" / "ckpt.pt"))

@@ -16,6 +16,7 @@ from neural_inventory_control_amd import _lib, small_rollout as sr, workloads
 from neural_inventory_control_amd.data_handling import Scenario
 from neural_inventory_control_amd.layout import EnvProblem, Table, to_soa
 from neural_inventory_control_amd.neural_networks import NeuralNetworkCreator
+from neural_inventory_control_amd.policy_layers import materialize_linears
 from neural_inventory_control_amd.rollout import FusedRollout
 from neural_inventory_control_amd.small_ensemble import SmallPolicyEnsemble
 from small_rollout_checks import SMALL_CASES
@@ -314,7 +315,7 @@ def _fresh_models(workload, B, T, seeds):
     for seed in seeds:
         torch.manual_seed(seed)
         m = NeuralNetworkCreator().create_neural_network(sc, policy, device=DEV)
-        FusedRollout(m, setting["problem_params"], DEV).materialize(F)
+        materialize_linears(m.master_linears(), F)
         models.append(m)
     return models
 

@@ -13,6 +13,7 @@ import torch
 from golden_io import Golden
 from neural_inventory_control_amd import _lib, build, horizon_ensemble as he, horizon_rollout as hz, small_rollout as sr
 from neural_inventory_control_amd.neural_networks import NeuralNetworkCreator
+from neural_inventory_control_amd.policy_layers import materialize_linears
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUFFERS = ("W1", "W2", "W3", "b2", "b3", "z1_obs", "rewards", "state_final", "state_hist", "h1_hist", "h2_hist", "logits_hist",
@@ -251,9 +252,7 @@ def _models(k, hidden=None, activation=None, policy=None, bias=True, materialize
         m = NeuralNetworkCreator().create_neural_network(_Sc(), nn_params, device="cpu")
         if materialize:
             F = g.params["net.master.0.weight"].shape[1]
-            eng = he.FusedRollout.__new__(he.FusedRollout)
-            eng.model = m
-            eng.materialize(F)
+            materialize_linears(m.master_linears(), F)
         out.append(m)
     return out, g
 

@@ -3,6 +3,7 @@ data), dataset plumbing, the policy factory, layout helpers, and the no-CPU-fall
 import copy
 import ctypes
 import re
+import types
 import os
 
 import numpy as np
@@ -14,6 +15,7 @@ from neural_inventory_control_amd import _lib, layout
 from neural_inventory_control_amd.data_handling import DatasetCreator, DeviceBatches, MyDataset, Scenario, Scenarios
 from neural_inventory_control_amd.environment import Simulator
 from neural_inventory_control_amd.neural_networks import NeuralNetworkCreator, VanillaWarehouse
+from neural_inventory_control_amd.policy_layers import materialize_linears
 from neural_inventory_control_amd.rollout import FusedRollout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -87,10 +89,8 @@ def test_policy_factory_and_state_dict_layout():
     # ("symmetry_aware" is not registered upstream - SURVEY facts; here it names this repository's recovered policy, round 3)
     assert NeuralNetworkCreator().get_architecture("symmetry_aware").__name__ == "SymmetryAware"
     # materialise like the engine does and load the reference's weights by key
-    eng = FusedRollout.__new__(FusedRollout)
-    eng.model = model
     F = 5 * 3 + 3
-    eng.materialize(F)
+    materialize_linears(model.master_linears(), F)
     assert set(model.state_dict().keys()) == set(g.params.keys())
     model.load_state_dict(g.params)
     assert NeuralNetworkCreator().set_default_output_size("master", {"n_stores": 64, "n_warehouses": 3}) == 195
@@ -235,9 +235,8 @@ def test_mlp_engine_routing_rules_for_the_data_driven_policy():
     relu_inside = copy.deepcopy(c["nn_params"])
     relu_inside["inner_layer_activations"]["master"] = "relu"
     assert not FusedRollout.supports(NeuralNetworkCreator().create_neural_network(_Sc(), relu_inside, device="cpu"))
-    eng = FusedRollout.__new__(FusedRollout)
-    eng.head = "data_driven"
-    assert eng.input_rows(g.data, obs) == g.params["net.master.0.weight"].shape[1]
+    eng = types.SimpleNamespace(head="data_driven")   # (what `input_rows` reads of its engine)
+    assert FusedRollout.input_rows(eng, g.data, obs) == g.params["net.master.0.weight"].shape[1]
     gv = Golden("cfg3_one_warehouse_5_vanilla")
     cv, scv = _scenario(gv)
     vanilla = NeuralNetworkCreator().create_neural_network(scv, cv["nn_params"], device="cpu")

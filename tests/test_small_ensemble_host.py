@@ -13,6 +13,7 @@ import torch
 from golden_io import Golden
 from neural_inventory_control_amd import _lib, build, ensemble_step as es, small_ensemble as se, small_rollout as sr
 from neural_inventory_control_amd.neural_networks import NeuralNetworkCreator
+from neural_inventory_control_amd.policy_layers import materialize_linears
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SLICES = ("weights", "rewards", "final_state", "states", "hidden", "logits", "slab_rows", "slab_row_stride", "slab", "grad", "scratch")
@@ -196,9 +197,7 @@ def _models(name, k, hidden=None, activation=None, materialize=True):
         m = NeuralNetworkCreator().create_neural_network(_Sc(), nn_params, device="cpu")
         if materialize:
             F = g.params["net.master.0.weight"].shape[1]
-            eng = se.FusedRollout.__new__(se.FusedRollout)
-            eng.model = m
-            eng.materialize(F)
+            materialize_linears(m.master_linears(), F)
         out.append(m)
     return out, g
 

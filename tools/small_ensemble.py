@@ -50,6 +50,7 @@ def measure(workload, scenarios, model_counts, T, reps):
     from neural_inventory_control_amd import _lib, workloads
     from neural_inventory_control_amd.data_handling import Scenario
     from neural_inventory_control_amd.neural_networks import NeuralNetworkCreator
+    from neural_inventory_control_amd.policy_layers import materialize_linears
     from neural_inventory_control_amd.rollout import FusedRollout
     from neural_inventory_control_amd.small_ensemble import SmallPolicyEnsemble
     dev = "cuda:0"
@@ -70,7 +71,7 @@ def measure(workload, scenarios, model_counts, T, reps):
             for seed in range(K):
                 torch.manual_seed(seed)
                 m = NeuralNetworkCreator().create_neural_network(sc, policy, device=dev)
-                FusedRollout(m, setting["problem_params"], dev).materialize(F)
+                materialize_linears(m.master_linears(), F)
                 models.append(m)
             ens = SmallPolicyEnsemble(models, setting["problem_params"], dev)
             singles = [FusedRollout(m, setting["problem_params"], dev) for m in models]

@@ -58,7 +58,7 @@ def measure(workload, scenarios, replicas, T, reps):
     from neural_inventory_control_amd.data_handling import Scenario
     from neural_inventory_control_amd.ensemble_adam import EnsembleAdam
     from neural_inventory_control_amd.neural_networks import NeuralNetworkCreator
-    from neural_inventory_control_amd.rollout import FusedRollout
+    from neural_inventory_control_amd.policy_layers import materialize_linears
     from neural_inventory_control_amd.small_ensemble import SmallPolicyEnsemble
     dev = "cuda:0"
     setting, policy, _, _, _ = workloads.get(workload)
@@ -82,7 +82,7 @@ def measure(workload, scenarios, replicas, T, reps):
             for seed in range(K):
                 torch.manual_seed(seed)
                 m = NeuralNetworkCreator().create_neural_network(sc, policy, device=dev)
-                FusedRollout(m, pp, dev).materialize(F)
+                materialize_linears(m.master_linears(), F)
                 ms.append(m)
             return ms
 

@@ -62,6 +62,7 @@ def measure(workload, scenarios, model_counts, T, reps):
     from neural_inventory_control_amd.data_handling import Scenario
     from neural_inventory_control_amd.ensemble_adam import EnsembleAdam
     from neural_inventory_control_amd.neural_networks import NeuralNetworkCreator
+    from neural_inventory_control_amd.policy_layers import materialize_linears
     from neural_inventory_control_amd.rollout import FusedRollout
     from neural_inventory_control_amd.small_ensemble import SmallPolicyEnsemble
     dev = "cuda:0"
@@ -84,7 +85,7 @@ def measure(workload, scenarios, model_counts, T, reps):
             for seed in range(K):
                 torch.manual_seed(seed)
                 m = NeuralNetworkCreator().create_neural_network(sc, policy, device=dev)
-                FusedRollout(m, pp, dev).materialize(F)
+                materialize_linears(m.master_linears(), F)
                 ms.append(m)
             return ms
         for K in model_counts:
