@@ -511,6 +511,20 @@ int nic_ensemble_adam_prepare(int32_t n_models, const double* hyper, NicEnsemble
 int nic_ensemble_adam_update(int32_t n_models, int32_t P, float* params, int64_t params_stride, const float* grads, int64_t grads_stride,
                              float* exp_avg, int64_t exp_avg_stride, float* exp_avg_sq, int64_t exp_avg_sq_stride, const float* coef,
                              void* stream);
+/* The same step with every model's total gradient norm clipped first (trainer.py:175-176's `clip_grad_norm_(model.parameters(),
+ * max_norm)`, once per model), still two launches.  max_norm [K] doubles on the device (+inf: that model is not clipped), clip
+ * [K][2] floats {scale, norm}.  The arithmetic is csrc/ensemble_clip_body.h's.
+ * `prepare_clipped` (grid K, one 256-thread workgroup per model): the sum of squares of the model's P gradient columns in double,
+ * in the header's fixed order (lane i adds columns i, i + 256, ...; the lane sums meet in a pairwise tree) - no atomics, columns
+ * at or past P are not read; norm = sqrt(sum), scale = max_norm == +inf ? 1 : min(1, max_norm / (norm + 1e-6)), each rounded to
+ * float once into clip; then `prepare`'s own work.  Sized for rows of 10^3 to 10^5 columns.
+ * `update_clipped`: `update` on g * scale (with scale == 1 the bits of `update`).
+ * Refused as above; also a null max_norm, clip or grads, and (prepare_clipped) P < 1 or a gradient stride shorter than P. */
+int nic_ensemble_adam_prepare_clipped(int32_t n_models, int32_t P, const double* hyper, const double* max_norm, NicEnsembleAdamState* state,
+                                      float* coef, const float* grads, int64_t grads_stride, float* clip, void* stream);
+int nic_ensemble_adam_update_clipped(int32_t n_models, int32_t P, float* params, int64_t params_stride, const float* grads,
+                                     int64_t grads_stride, float* exp_avg, int64_t exp_avg_stride, float* exp_avg_sq,
+                                     int64_t exp_avg_sq_stride, const float* coef, const float* clip, void* stream);
 
 /* ---- whole-horizon rollout of the closed-form policies ---------------------------------------------------------
  * base_stock (neural_networks.py:216-229), capped_base_stock (:296-311) and echelon_stock (:231-294) for T periods of

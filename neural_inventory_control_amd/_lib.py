@@ -259,6 +259,8 @@ PROTOTYPES = {
                                                         C.POINTER(NicSmallInstances), _vp, _vp, _vp, NicTable2, _vp, _i64, _vp]),
     "nic_ensemble_adam_prepare": (C.c_int, [_i32, _vp, _vp, _vp, _vp]),
     "nic_ensemble_adam_update": (C.c_int, [_i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "nic_ensemble_adam_prepare_clipped": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "nic_ensemble_adam_update_clipped": (C.c_int, [_i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "nic_horizon_rollout_ok": (C.c_int, [C.POINTER(NicHorizonDesc)]),
     "nic_horizon_rollout_fwd": (C.c_int, [C.POINTER(NicHorizonDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nic_horizon_rollout_bwd": (C.c_int, [C.POINTER(NicHorizonDesc), _vp, _vp, _vp, _vp, _vp, NicTable2, _vp, _vp, _vp, _vp]),

@@ -37,7 +37,7 @@ SOURCES = [
 EXPERIMENTS = os.environ.get("NIC_BUILD_EXPERIMENTS", "") not in ("", "0")
 if EXPERIMENTS:
     SOURCES.append((os.path.join(HERE, "..", "tools", "experiments", "wide_rollout.hip"), ["-ffp-contract=off", "-I", CSRC]))
-HEADERS = ["nic_common.h", "env_step_body.h", "policy_heads_body.h", "tail_pieces.h", "small_rollout_body.h", "small_rollout16.h", "closed_form_body.h", "gnn_alloc_body.h", "nic_bf16.h", "wgrad_plan.h", "wx_plan.h", "small_ensemble_plan.h", "horizon_ensemble_plan.h", "linear_models_plan.h", "ensemble_adam_body.h", "small_rollout_variants.h", "small_rollout_mfma.h", os.path.join("..", "..", "include", "nic_rollout.h")]
+HEADERS = ["nic_common.h", "env_step_body.h", "policy_heads_body.h", "tail_pieces.h", "small_rollout_body.h", "small_rollout16.h", "closed_form_body.h", "gnn_alloc_body.h", "nic_bf16.h", "wgrad_plan.h", "wx_plan.h", "small_ensemble_plan.h", "horizon_ensemble_plan.h", "linear_models_plan.h", "ensemble_adam_body.h", "ensemble_clip_body.h","small_rollout_variants.h", "small_rollout_mfma.h", os.path.join("..", "..", "include", "nic_rollout.h")]
 if EXPERIMENTS:
     HEADERS.append(os.path.join("..", "..", "include", "nic_experiments.h"))
 ARCH = "gfx950"

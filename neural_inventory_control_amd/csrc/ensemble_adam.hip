@@ -5,8 +5,11 @@
 // loads and stores (K x P is a few tens of thousands of floats and the weights' row stride P is odd: launch latency bounds it).
 // Built with -ffp-contract=off; float division and square root are the correctly rounded ones (hipcc's default).  Nothing here
 // knows about layers.
+// nic_ensemble_adam_prepare_clipped / _update_clipped: the same step with every model's total gradient norm clipped first
+// (trainer.py:175-176's `clip_grad_norm_`), arithmetic in csrc/ensemble_clip_body.h - still two launches, further down.
 #include "nic_common.h"
 #include "ensemble_adam_body.h"
+#include "ensemble_clip_body.h"
 
 namespace {
 constexpr int kT = nic::kEaThreads;
@@ -28,6 +31,42 @@ __global__ __launch_bounds__(kT) void ensemble_adam_update_kernel(int P, float* 
     const int64_t m = blockIdx.y;
     nic::ea_update(params + m * params_stride + col, grads[m * grads_stride + col], exp_avg + m * exp_avg_stride + col,
                    exp_avg_sq + m * exp_avg_sq_stride + col, coef + m * nic::EA_COEF_COUNT);
+}
+
+// ---- the same step with every model's gradient norm clipped (csrc/ensemble_clip_body.h) -------------------------------------------
+// grid K, one workgroup per model: thread i adds the squares of columns i, i + 256, ... of the model's gradient row in double, the
+// 256 lane sums meet in LDS in the header's tree order, thread 0 finishes the model (norm, scale, then the unclipped prepare).
+// Columns at or past P are never read.  No launch of its own for the norm and no atomics: the order of the additions is fixed.
+__global__ __launch_bounds__(kT) void ensemble_adam_prepare_clipped_kernel(int P, const double* __restrict__ hyper,
+                                                                           const double* __restrict__ max_norm,
+                                                                           nic::EaState* __restrict__ state, float* __restrict__ coef,
+                                                                           const float* __restrict__ grads, int64_t grads_stride,
+                                                                           float* __restrict__ clip) {
+    __shared__ double lanes[kT];
+    const int64_t m = blockIdx.x;
+    const int lane = threadIdx.x;
+    lanes[lane] = nic::ec_lane_sum(grads + m * grads_stride, P, lane);
+    __syncthreads();
+    for (int stride = kT / 2; stride >= 1; stride >>= 1) {
+        if (lane < stride) nic::ec_combine(lanes, lane, stride);
+        __syncthreads();
+    }
+    if (lane == 0)
+        nic::ec_finish(lanes[0], max_norm[m], hyper + m * nic::EA_HYPER_COUNT, state + m, coef + m * nic::EA_COEF_COUNT,
+                       clip + m * nic::EC_CLIP_COUNT);
+}
+
+// the update's grid and bounds; the gradient is scaled by the model's clip[EC_SCALE] on its way into the unchanged body
+__global__ __launch_bounds__(kT) void ensemble_adam_update_clipped_kernel(int P, float* __restrict__ params, int64_t params_stride,
+                                                                          const float* __restrict__ grads, int64_t grads_stride,
+                                                                          float* __restrict__ exp_avg, int64_t exp_avg_stride,
+                                                                          float* __restrict__ exp_avg_sq, int64_t exp_avg_sq_stride,
+                                                                          const float* __restrict__ coef, const float* __restrict__ clip) {
+    const int col = blockIdx.x * kT + threadIdx.x;
+    if (col >= P) return;
+    const int64_t m = blockIdx.y;
+    nic::ec_update(params + m * params_stride + col, grads[m * grads_stride + col], clip[m * nic::EC_CLIP_COUNT + nic::EC_SCALE],
+                   exp_avg + m * exp_avg_stride + col, exp_avg_sq + m * exp_avg_sq_stride + col, coef + m * nic::EA_COEF_COUNT);
 }
 }  // namespace
 
@@ -53,6 +92,30 @@ int nic_ensemble_adam_update(int32_t n_models, int32_t P, float* params, int64_t
     hipLaunchKernelGGL(ensemble_adam_update_kernel, dim3(nic::ceil_div(P, kT), n_models), dim3(kT), 0, nic::as_stream(stream), P, params,
                        params_stride, grads, grads_stride, exp_avg, exp_avg_stride, exp_avg_sq, exp_avg_sq_stride, coef);
     return nic::check_launch("nic_ensemble_adam_update");
+}
+
+int nic_ensemble_adam_prepare_clipped(int32_t n_models, int32_t P, const double* hyper, const double* max_norm, NicEnsembleAdamState* state,
+                                      float* coef, const float* grads, int64_t grads_stride, float* clip, void* stream) {
+    const int why = nic::ec_check_prepare(n_models, P, hyper, max_norm, state, coef, grads, grads_stride, clip);
+    NIC_REQUIRE(why == 0, "nic_ensemble_adam_prepare_clipped: %s (%d models, P = %d, gradient stride %lld)", nic::ea_reason(why), n_models, P,
+                (long long)grads_stride);
+    nic::note_kernelf("ensemble_adam_prepare_clipped<%d,models=%d>", P, n_models);
+    hipLaunchKernelGGL(ensemble_adam_prepare_clipped_kernel, dim3(n_models), dim3(kT), 0, nic::as_stream(stream), P, hyper, max_norm, state,
+                       coef, grads, grads_stride, clip);
+    return nic::check_launch("nic_ensemble_adam_prepare_clipped");
+}
+
+int nic_ensemble_adam_update_clipped(int32_t n_models, int32_t P, float* params, int64_t params_stride, const float* grads,
+                                     int64_t grads_stride, float* exp_avg, int64_t exp_avg_stride, float* exp_avg_sq,
+                                     int64_t exp_avg_sq_stride, const float* coef, const float* clip, void* stream) {
+    const int why = nic::ec_check_update(n_models, P, params, params_stride, grads, grads_stride, exp_avg, exp_avg_stride, exp_avg_sq,
+                                         exp_avg_sq_stride, coef, clip);
+    NIC_REQUIRE(why == 0, "nic_ensemble_adam_update_clipped: %s (%d models, P = %d, strides %lld %lld %lld %lld)", nic::ea_reason(why), n_models,
+                P, (long long)params_stride, (long long)grads_stride, (long long)exp_avg_stride, (long long)exp_avg_sq_stride);
+    nic::note_kernelf("ensemble_adam_update_clipped<%d,models=%d>", P, n_models);
+    hipLaunchKernelGGL(ensemble_adam_update_clipped_kernel, dim3(nic::ceil_div(P, kT), n_models), dim3(kT), 0, nic::as_stream(stream), P,
+                       params, params_stride, grads, grads_stride, exp_avg, exp_avg_stride, exp_avg_sq, exp_avg_sq_stride, coef, clip);
+    return nic::check_launch("nic_ensemble_adam_update_clipped");
 }
 
 }  // extern "C"

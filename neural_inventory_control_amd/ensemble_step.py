@@ -283,6 +283,24 @@ class EnsembleStep:
             raise ValueError(f"{type(self).__name__}.train_step: the optimizer is for {optimizer.n_models} models of {optimizer.P} "
                              f"parameters, the engine has {self.weights.shape[0]} of {self.weights.shape[1]}")
 
+    def make_optimizer(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm="models"):
+        """An `EnsembleAdam` for this engine's (K, P) and parameter shapes.  `max_grad_norm`: "models" clips model m's gradient norm at
+        its `gradient_clipping_norm_value` as the trainer does (trainer.py:175-176; None there: that model is not clipped, and with
+        no model that has one the optimizer is an unclipped one); else what `EnsembleAdam` takes.  Needs sized weights: bound
+        parameters or a first batch."""
+        if self.weights is None:
+            raise ValueError(f"{type(self).__name__}.make_optimizer needs sized weights: bind_parameters() on materialised models, or a "
+                             "first batch")
+        if isinstance(max_grad_norm, str):
+            if max_grad_norm != "models":
+                raise ValueError(f"{type(self).__name__}.make_optimizer: max_grad_norm is \"models\", None, a number or one per model")
+            max_grad_norm = [getattr(m, "gradient_clipping_norm_value", None) for m in self.models]
+            if all(v is None for v in max_grad_norm):
+                max_grad_norm = None
+        K, P = self.weights.shape
+        return EnsembleAdam(K, P, self.device, lr, betas=betas, eps=eps, weight_decay=weight_decay, param_shapes=self.param_shapes,
+                            max_grad_norm=max_grad_norm)
+
     # ---- epochs ------------------------------------------------------------------------------------------------------------------
     def fit(self, train_batches, dev_batches, epochs, periods, dev_periods, ignore_periods, optimizer, observation_params=None):
         """`epochs` times: `train_step` over `train_batches`, then `run(train=False)` over `dev_batches` (each batch a dict, or -

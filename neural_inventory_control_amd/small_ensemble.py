@@ -292,8 +292,7 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
         # sequence holds, are part of the capture's key, so evaluations in between (`fit`) change nothing
         if replay.on():
             replay.set_variant((K,) + variant + (self.small_lane_scenarios, self.weights.data_ptr(), ub))
-        opt_key = optimizer and tuple(t.data_ptr() for t in (optimizer.hyper, optimizer.state, optimizer.coef, optimizer.exp_avg,
-                                                               optimizer.exp_avg_sq))
+        opt_key = optimizer and optimizer.capture_key()   # (clipping on or off is part of it: the two run other launches)
         replay.probe_begin(train)
         replay.call((train, opt_key, ignore_periods, shift, bool(discrete_allocation), width) + key, launches)
         replay.probe_end()
