@@ -487,6 +487,33 @@ int nic_small_rollout_instances_bwd_wgrad(const NicSmallRolloutDesc* d, const Ni
                                           const float* states_hist, const float* hidden_hist, const float* logits_hist,
                                           NicTable2 g_reward, float* slab, int64_t slab_row_stride, void* stream);
 
+/* ---- The active-model mask: models that have stopped training leave the K-model launches --------------------------------------
+ * Per-model early stopping (trainer.py:188-197, once per model) in a sweep: `active` is int32 [n_models] on the device, non-zero =
+ * the model runs, NULL = every model runs.  Each entry point below is the one it is named after with the mask as one more
+ * argument.  The grid stays (x, K): every workgroup of a model whose entry is zero returns at entry - one scalar load and a branch
+ * ahead of its first load or store - so NO byte of that model's slices is read or written: rewards, final state, the three
+ * histories, the slab, grad, its totals row and its reduce scratch keep what they held.  For a model that runs, every output is
+ * the bits of the entry point without the mask.  The mask is read when the kernels run, so a replayed capture follows its
+ * current contents.
+ * The checks are the unmasked entry points' plus csrc/small_ensemble_plan.h's small_ensemble_check_active: a non-NULL mask must be
+ * 4-byte aligned.  The mask's CONTENTS are device memory and cannot be checked on the host: the caller owns that it holds
+ * n_models entries. */
+int nic_small_rollout_ensemble_fwd_active(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, float* rewards, float* state_final,
+                                          float* states_hist, float* hidden_hist, float* logits_hist, const int32_t* active, void* stream);
+int nic_small_rollout_ensemble_bwd_wgrad_active(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const float* states_hist,
+                                                const float* hidden_hist, const float* logits_hist, NicTable2 g_reward, float* slab,
+                                                int64_t slab_row_stride, const int32_t* active, void* stream);
+int nic_small_rollout_ensemble_reduce_active(const NicSmallEnsemble* e, const float* slab, int32_t n_rows, int64_t slab_row_stride, int32_t P,
+                                             float* grad, const float* rewards, int64_t n_reward_elems, int64_t ignore_elems,
+                                             float* totals, float* scratch, const int32_t* active, void* stream);
+int nic_small_rollout_instances_fwd_active(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst,
+                                           float* rewards, float* state_final, float* states_hist, float* hidden_hist,
+                                           float* logits_hist, const int32_t* active, void* stream);
+int nic_small_rollout_instances_bwd_wgrad_active(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst,
+                                                 const float* states_hist, const float* hidden_hist, const float* logits_hist,
+                                                 NicTable2 g_reward, float* slab, int64_t slab_row_stride, const int32_t* active,
+                                                 void* stream);
+
 /* ---- Adam for K models whose parameters are rows of one buffer: two launches per step for all of them -------------------------
  * Replaces main_run.py:110 (`torch.optim.Adam(model.parameters(), lr=...)`) stepped by trainer.py:177 (`optimizer.step()`), once per
  * model (K optimizers, or K parameter groups: torch launches per group).  Row m of params / grads / exp_avg / exp_avg_sq starts
@@ -525,6 +552,18 @@ int nic_ensemble_adam_prepare_clipped(int32_t n_models, int32_t P, const double*
 int nic_ensemble_adam_update_clipped(int32_t n_models, int32_t P, float* params, int64_t params_stride, const float* grads,
                                      int64_t grads_stride, float* exp_avg, int64_t exp_avg_stride, float* exp_avg_sq,
                                      int64_t exp_avg_sq_stride, const float* coef, const float* clip, void* stream);
+/* Either step under the active-model mask (`active` int32 [K] on the device, non-zero = the model takes the step, NULL = all):
+ * ONE pair for both - max_norm, clip and (for `prepare_active`) grads all NULL is the unclipped step, all non-NULL the clipped one
+ * (P and grads_stride are read only then).  A model whose entry is zero sits the step out: `prepare_active` leaves its step
+ * counter, c1, c2, its coef row and its clip row alone, `update_active` its rows of params, exp_avg and exp_avg_sq, and none of its
+ * gradient row is read.  The arithmetic is unchanged: a model that steps gets the bits of the unmasked pair.  Refused as above;
+ * also max_norm / clip / grads not going together and a mask that is not 4-byte aligned.  The mask's contents are device memory
+ * and cannot be checked on the host. */
+int nic_ensemble_adam_prepare_active(int32_t n_models, int32_t P, const double* hyper, const double* max_norm, NicEnsembleAdamState* state,
+                                     float* coef, const float* grads, int64_t grads_stride, float* clip, const int32_t* active, void* stream);
+int nic_ensemble_adam_update_active(int32_t n_models, int32_t P, float* params, int64_t params_stride, const float* grads,
+                                    int64_t grads_stride, float* exp_avg, int64_t exp_avg_stride, float* exp_avg_sq,
+                                    int64_t exp_avg_sq_stride, const float* coef, const float* clip, const int32_t* active, void* stream);
 
 /* ---- whole-horizon rollout of the closed-form policies ---------------------------------------------------------
  * base_stock (neural_networks.py:216-229), capped_base_stock (:296-311) and echelon_stock (:231-294) for T periods of

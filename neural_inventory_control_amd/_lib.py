@@ -261,6 +261,19 @@ PROTOTYPES = {
     "nic_ensemble_adam_update": (C.c_int, [_i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp]),
     "nic_ensemble_adam_prepare_clipped": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "nic_ensemble_adam_update_clipped": (C.c_int, [_i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    # the active-model mask: the entry point it is named after with `active` (int32 [K] on the device, or NULL) ahead of the stream
+    "nic_small_rollout_ensemble_fwd_active": (C.c_int, [C.POINTER(NicSmallRolloutDesc), C.POINTER(NicSmallEnsemble), _vp, _vp, _vp, _vp, _vp,
+                                                        _vp, _vp]),
+    "nic_small_rollout_ensemble_bwd_wgrad_active": (C.c_int, [C.POINTER(NicSmallRolloutDesc), C.POINTER(NicSmallEnsemble), _vp, _vp, _vp,
+                                                              NicTable2, _vp, _i64, _vp, _vp]),
+    "nic_small_rollout_ensemble_reduce_active": (C.c_int, [C.POINTER(NicSmallEnsemble), _vp, _i32, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _vp,
+                                                           _vp, _vp]),
+    "nic_small_rollout_instances_fwd_active": (C.c_int, [C.POINTER(NicSmallRolloutDesc), C.POINTER(NicSmallEnsemble),
+                                                         C.POINTER(NicSmallInstances), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nic_small_rollout_instances_bwd_wgrad_active": (C.c_int, [C.POINTER(NicSmallRolloutDesc), C.POINTER(NicSmallEnsemble),
+                                                               C.POINTER(NicSmallInstances), _vp, _vp, _vp, NicTable2, _vp, _i64, _vp, _vp]),
+    "nic_ensemble_adam_prepare_active": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "nic_ensemble_adam_update_active": (C.c_int, [_i32, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "nic_horizon_rollout_ok": (C.c_int, [C.POINTER(NicHorizonDesc)]),
     "nic_horizon_rollout_fwd": (C.c_int, [C.POINTER(NicHorizonDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "nic_horizon_rollout_bwd": (C.c_int, [C.POINTER(NicHorizonDesc), _vp, _vp, _vp, _vp, _vp, NicTable2, _vp, _vp, _vp, _vp]),

@@ -15,9 +15,9 @@ namespace {
 constexpr int kT = nic::kEaThreads;
 
 __global__ __launch_bounds__(kT) void ensemble_adam_prepare_kernel(int n_models, const double* __restrict__ hyper, nic::EaState* __restrict__ state,
-                                                                   float* __restrict__ coef) {
+                                                                   float* __restrict__ coef, const int32_t* __restrict__ active) {
     const int m = blockIdx.x * kT + threadIdx.x;
-    if (m < n_models) nic::ea_prepare(hyper + (int64_t)m * nic::EA_HYPER_COUNT, state + m, coef + (int64_t)m * nic::EA_COEF_COUNT);
+    if (m < n_models && nic::ea_model_steps(active, m)) nic::ea_prepare(hyper + (int64_t)m * nic::EA_HYPER_COUNT, state + m, coef + (int64_t)m * nic::EA_COEF_COUNT);
 }
 
 // grid (ceil(P / 256), K): columns at or past P of a row are neither read nor written
@@ -25,10 +25,11 @@ __global__ __launch_bounds__(kT) void ensemble_adam_update_kernel(int P, float* 
                                                                   const float* __restrict__ grads, int64_t grads_stride,
                                                                   float* __restrict__ exp_avg, int64_t exp_avg_stride,
                                                                   float* __restrict__ exp_avg_sq, int64_t exp_avg_sq_stride,
-                                                                  const float* __restrict__ coef) {
+                                                                  const float* __restrict__ coef, const int32_t* __restrict__ active) {
+    const int64_t m = blockIdx.y;
+    if (!nic::ea_model_steps(active, m)) return;   // (wave-uniform: the model's rows are neither read nor written)
     const int col = blockIdx.x * kT + threadIdx.x;
     if (col >= P) return;
-    const int64_t m = blockIdx.y;
     nic::ea_update(params + m * params_stride + col, grads[m * grads_stride + col], exp_avg + m * exp_avg_stride + col,
                    exp_avg_sq + m * exp_avg_sq_stride + col, coef + m * nic::EA_COEF_COUNT);
 }
@@ -41,9 +42,10 @@ __global__ __launch_bounds__(kT) void ensemble_adam_prepare_clipped_kernel(int P
                                                                            const double* __restrict__ max_norm,
                                                                            nic::EaState* __restrict__ state, float* __restrict__ coef,
                                                                            const float* __restrict__ grads, int64_t grads_stride,
-                                                                           float* __restrict__ clip) {
+                                                                           float* __restrict__ clip, const int32_t* __restrict__ active) {
     __shared__ double lanes[kT];
     const int64_t m = blockIdx.x;
+    if (!nic::ea_model_steps(active, m)) return;   // (the whole workgroup, ahead of the barriers)
     const int lane = threadIdx.x;
     lanes[lane] = nic::ec_lane_sum(grads + m * grads_stride, P, lane);
     __syncthreads();
@@ -61,12 +63,44 @@ __global__ __launch_bounds__(kT) void ensemble_adam_update_clipped_kernel(int P,
                                                                           const float* __restrict__ grads, int64_t grads_stride,
                                                                           float* __restrict__ exp_avg, int64_t exp_avg_stride,
                                                                           float* __restrict__ exp_avg_sq, int64_t exp_avg_sq_stride,
-                                                                          const float* __restrict__ coef, const float* __restrict__ clip) {
+                                                                          const float* __restrict__ coef, const float* __restrict__ clip,
+                                                                          const int32_t* __restrict__ active) {
+    const int64_t m = blockIdx.y;
+    if (!nic::ea_model_steps(active, m)) return;
     const int col = blockIdx.x * kT + threadIdx.x;
     if (col >= P) return;
-    const int64_t m = blockIdx.y;
     nic::ec_update(params + m * params_stride + col, grads[m * grads_stride + col], clip[m * nic::EC_CLIP_COUNT + nic::EC_SCALE],
                    exp_avg + m * exp_avg_stride + col, exp_avg_sq + m * exp_avg_sq_stride + col, coef + m * nic::EA_COEF_COUNT);
+}
+// the launches behind the entry points; `tag`: "" or ",active" (the recorded name of the existing entry points stays theirs)
+int launch_prepare(int32_t n_models, int32_t P, const double* hyper, const double* max_norm, NicEnsembleAdamState* state, float* coef,
+                   const float* grads, int64_t grads_stride, float* clip, const int32_t* active, const char* tag, void* stream, const char* who) {
+    if (max_norm) {
+        nic::note_kernelf("ensemble_adam_prepare_clipped<%d,models=%d%s>", P, n_models, tag);
+        hipLaunchKernelGGL(ensemble_adam_prepare_clipped_kernel, dim3(n_models), dim3(kT), 0, nic::as_stream(stream), P, hyper, max_norm, state,
+                           coef, grads, grads_stride, clip, active);
+    } else {
+        nic::note_kernelf("ensemble_adam_prepare<models=%d%s>", n_models, tag);
+        hipLaunchKernelGGL(ensemble_adam_prepare_kernel, dim3(nic::ceil_div(n_models, kT)), dim3(kT), 0, nic::as_stream(stream), n_models, hyper,
+                           state, coef, active);
+    }
+    return nic::check_launch(who);
+}
+
+int launch_update(int32_t n_models, int32_t P, float* params, int64_t params_stride, const float* grads, int64_t grads_stride, float* exp_avg,
+                  int64_t exp_avg_stride, float* exp_avg_sq, int64_t exp_avg_sq_stride, const float* coef, const float* clip,
+                  const int32_t* active, const char* tag, void* stream, const char* who) {
+    const dim3 grid(nic::ceil_div(P, kT), n_models);
+    if (clip) {
+        nic::note_kernelf("ensemble_adam_update_clipped<%d,models=%d%s>", P, n_models, tag);
+        hipLaunchKernelGGL(ensemble_adam_update_clipped_kernel, grid, dim3(kT), 0, nic::as_stream(stream), P, params, params_stride, grads,
+                           grads_stride, exp_avg, exp_avg_stride, exp_avg_sq, exp_avg_sq_stride, coef, clip, active);
+    } else {
+        nic::note_kernelf("ensemble_adam_update<%d,models=%d%s>", P, n_models, tag);
+        hipLaunchKernelGGL(ensemble_adam_update_kernel, grid, dim3(kT), 0, nic::as_stream(stream), P, params, params_stride, grads,
+                           grads_stride, exp_avg, exp_avg_stride, exp_avg_sq, exp_avg_sq_stride, coef, active);
+    }
+    return nic::check_launch(who);
 }
 }  // namespace
 
@@ -75,10 +109,7 @@ extern "C" {
 int nic_ensemble_adam_prepare(int32_t n_models, const double* hyper, NicEnsembleAdamState* state, float* coef, void* stream) {
     const int why = nic::ea_check_prepare(n_models, hyper, state, coef);
     NIC_REQUIRE(why == 0, "nic_ensemble_adam_prepare: %s (%d models)", nic::ea_reason(why), n_models);
-    nic::note_kernelf("ensemble_adam_prepare<models=%d>", n_models);
-    hipLaunchKernelGGL(ensemble_adam_prepare_kernel, dim3(nic::ceil_div(n_models, kT)), dim3(kT), 0, nic::as_stream(stream), n_models, hyper,
-                       state, coef);
-    return nic::check_launch("nic_ensemble_adam_prepare");
+    return launch_prepare(n_models, 0, hyper, nullptr, state, coef, nullptr, 0, nullptr, nullptr, "", stream, "nic_ensemble_adam_prepare");
 }
 
 int nic_ensemble_adam_update(int32_t n_models, int32_t P, float* params, int64_t params_stride, const float* grads, int64_t grads_stride,
@@ -88,10 +119,8 @@ int nic_ensemble_adam_update(int32_t n_models, int32_t P, float* params, int64_t
                                          exp_avg_sq_stride, coef);
     NIC_REQUIRE(why == 0, "nic_ensemble_adam_update: %s (%d models, P = %d, strides %lld %lld %lld %lld)", nic::ea_reason(why), n_models, P,
                 (long long)params_stride, (long long)grads_stride, (long long)exp_avg_stride, (long long)exp_avg_sq_stride);
-    nic::note_kernelf("ensemble_adam_update<%d,models=%d>", P, n_models);
-    hipLaunchKernelGGL(ensemble_adam_update_kernel, dim3(nic::ceil_div(P, kT), n_models), dim3(kT), 0, nic::as_stream(stream), P, params,
-                       params_stride, grads, grads_stride, exp_avg, exp_avg_stride, exp_avg_sq, exp_avg_sq_stride, coef);
-    return nic::check_launch("nic_ensemble_adam_update");
+    return launch_update(n_models, P, params, params_stride, grads, grads_stride, exp_avg, exp_avg_stride, exp_avg_sq, exp_avg_sq_stride, coef,
+                         nullptr, nullptr, "", stream, "nic_ensemble_adam_update");
 }
 
 int nic_ensemble_adam_prepare_clipped(int32_t n_models, int32_t P, const double* hyper, const double* max_norm, NicEnsembleAdamState* state,
@@ -99,10 +128,8 @@ int nic_ensemble_adam_prepare_clipped(int32_t n_models, int32_t P, const double*
     const int why = nic::ec_check_prepare(n_models, P, hyper, max_norm, state, coef, grads, grads_stride, clip);
     NIC_REQUIRE(why == 0, "nic_ensemble_adam_prepare_clipped: %s (%d models, P = %d, gradient stride %lld)", nic::ea_reason(why), n_models, P,
                 (long long)grads_stride);
-    nic::note_kernelf("ensemble_adam_prepare_clipped<%d,models=%d>", P, n_models);
-    hipLaunchKernelGGL(ensemble_adam_prepare_clipped_kernel, dim3(n_models), dim3(kT), 0, nic::as_stream(stream), P, hyper, max_norm, state,
-                       coef, grads, grads_stride, clip);
-    return nic::check_launch("nic_ensemble_adam_prepare_clipped");
+    return launch_prepare(n_models, P, hyper, max_norm, state, coef, grads, grads_stride, clip, nullptr, "", stream,
+                          "nic_ensemble_adam_prepare_clipped");
 }
 
 int nic_ensemble_adam_update_clipped(int32_t n_models, int32_t P, float* params, int64_t params_stride, const float* grads,
@@ -112,10 +139,29 @@ int nic_ensemble_adam_update_clipped(int32_t n_models, int32_t P, float* params,
                                          exp_avg_sq_stride, coef, clip);
     NIC_REQUIRE(why == 0, "nic_ensemble_adam_update_clipped: %s (%d models, P = %d, strides %lld %lld %lld %lld)", nic::ea_reason(why), n_models,
                 P, (long long)params_stride, (long long)grads_stride, (long long)exp_avg_stride, (long long)exp_avg_sq_stride);
-    nic::note_kernelf("ensemble_adam_update_clipped<%d,models=%d>", P, n_models);
-    hipLaunchKernelGGL(ensemble_adam_update_clipped_kernel, dim3(nic::ceil_div(P, kT), n_models), dim3(kT), 0, nic::as_stream(stream), P,
-                       params, params_stride, grads, grads_stride, exp_avg, exp_avg_stride, exp_avg_sq, exp_avg_sq_stride, coef, clip);
-    return nic::check_launch("nic_ensemble_adam_update_clipped");
+    return launch_update(n_models, P, params, params_stride, grads, grads_stride, exp_avg, exp_avg_stride, exp_avg_sq, exp_avg_sq_stride, coef,
+                         clip, nullptr, "", stream, "nic_ensemble_adam_update_clipped");
+}
+
+/* either step under the active-model mask: max_norm / clip NULL is the unclipped pair, else the clipped one */
+int nic_ensemble_adam_prepare_active(int32_t n_models, int32_t P, const double* hyper, const double* max_norm, NicEnsembleAdamState* state,
+                                     float* coef, const float* grads, int64_t grads_stride, float* clip, const int32_t* active, void* stream) {
+    const int why = nic::ea_check_prepare_active(n_models, P, hyper, max_norm, state, coef, grads, grads_stride, clip, active);
+    NIC_REQUIRE(why == 0, "nic_ensemble_adam_prepare_active: %s (%d models, P = %d, gradient stride %lld)", nic::ea_reason(why), n_models, P,
+                (long long)grads_stride);
+    return launch_prepare(n_models, P, hyper, max_norm, state, coef, grads, grads_stride, clip, active, ",active", stream,
+                          "nic_ensemble_adam_prepare_active");
+}
+
+int nic_ensemble_adam_update_active(int32_t n_models, int32_t P, float* params, int64_t params_stride, const float* grads,
+                                    int64_t grads_stride, float* exp_avg, int64_t exp_avg_stride, float* exp_avg_sq,
+                                    int64_t exp_avg_sq_stride, const float* coef, const float* clip, const int32_t* active, void* stream) {
+    const int why = nic::ea_check_update_active(n_models, P, params, params_stride, grads, grads_stride, exp_avg, exp_avg_stride, exp_avg_sq,
+                                                exp_avg_sq_stride, coef, active);
+    NIC_REQUIRE(why == 0, "nic_ensemble_adam_update_active: %s (%d models, P = %d, strides %lld %lld %lld %lld)", nic::ea_reason(why), n_models,
+                P, (long long)params_stride, (long long)grads_stride, (long long)exp_avg_stride, (long long)exp_avg_sq_stride);
+    return launch_update(n_models, P, params, params_stride, grads, grads_stride, exp_avg, exp_avg_stride, exp_avg_sq, exp_avg_sq_stride, coef,
+                         clip, active, ",active", stream, "nic_ensemble_adam_update_active");
 }
 
 }  // extern "C"

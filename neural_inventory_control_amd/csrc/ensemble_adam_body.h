@@ -59,7 +59,8 @@ NIC_EA_FN void ea_update(float* p, float g, float* exp_avg, float* exp_avg_sq, c
 
 // ---- checks ----------------------------------------------------------------------------------------------------------------------
 // what a request is refused for (0: accepted); ea_reason names them
-enum EaRefusal { EA_OK = 0, EA_MODELS, EA_COLUMNS, EA_NULL, EA_PARAMS_STRIDE, EA_GRADS_STRIDE, EA_EXP_AVG_STRIDE, EA_EXP_AVG_SQ_STRIDE };
+enum EaRefusal { EA_OK = 0, EA_MODELS, EA_COLUMNS, EA_NULL, EA_PARAMS_STRIDE, EA_GRADS_STRIDE, EA_EXP_AVG_STRIDE, EA_EXP_AVG_SQ_STRIDE,
+                 EA_ACTIVE, EA_CLIP_TOGETHER };
 NIC_EA_FN const char* ea_reason(int r) {
     switch (r) {
         case EA_OK: return "accepted";
@@ -70,6 +71,8 @@ NIC_EA_FN const char* ea_reason(int r) {
         case EA_GRADS_STRIDE: return "gradient stride shorter than P";
         case EA_EXP_AVG_STRIDE: return "exp_avg stride shorter than P";
         case EA_EXP_AVG_SQ_STRIDE: return "exp_avg_sq stride shorter than P";
+        case EA_ACTIVE: return "the active mask must be NULL or 4-byte aligned";
+        case EA_CLIP_TOGETHER: return "max_norm, clip and the gradients go together";
         default: return "?";
     }
 }
@@ -89,6 +92,34 @@ NIC_EA_FN int ea_check_update(int n_models, int P, const void* params, int64_t p
     if (exp_avg_stride < P) return EA_EXP_AVG_STRIDE;
     if (exp_avg_sq_stride < P) return EA_EXP_AVG_SQ_STRIDE;
     return EA_OK;
+}
+
+// ---- the active-model mask (nic_ensemble_adam_prepare_active / _update_active) ------------------------------------------------------
+// `active`: int32 [n_models] on the device, non-zero = the model takes this step; NULL = every model does.  The mask decides whether
+// `ea_prepare` / `ea_update` (or the clipped pair) are CALLED for a model - their arithmetic is untouched - so a model that sits a
+// step out keeps its counter, its products, its coef / clip rows and its rows of params and moments to the bit.  Its contents are
+// device memory: the host can refuse the address only.
+NIC_EA_FN bool ea_model_steps(const int32_t* active, int64_t m) { return active == nullptr || active[m] != 0; }
+NIC_EA_FN int ea_check_active(const void* active) { return ((uintptr_t)active & 3) == 0 ? EA_OK : EA_ACTIVE; }
+// one pair serves both steps: max_norm == NULL is the unclipped one (then clip and, for `prepare`, grads are NULL too)
+NIC_EA_FN int ea_check_prepare_active(int n_models, int P, const void* hyper, const void* max_norm, const void* state, const void* coef,
+                                      const void* grads, int64_t grads_stride, const void* clip, const void* active) {
+    if (n_models < 1 || n_models > kEaMaxModels) return EA_MODELS;
+    if (!hyper || !state || !coef) return EA_NULL;
+    if ((max_norm != nullptr) != (clip != nullptr) || (max_norm != nullptr) != (grads != nullptr)) return EA_CLIP_TOGETHER;
+    if (max_norm) {
+        if (P < 1) return EA_COLUMNS;
+        if (grads_stride < P) return EA_GRADS_STRIDE;
+    }
+    return ea_check_active(active);
+}
+NIC_EA_FN int ea_check_update_active(int n_models, int P, const void* params, int64_t params_stride, const void* grads, int64_t grads_stride,
+                                     const void* exp_avg, int64_t exp_avg_stride, const void* exp_avg_sq, int64_t exp_avg_sq_stride,
+                                     const void* coef, const void* active) {
+    if (const int r = ea_check_update(n_models, P, params, params_stride, grads, grads_stride, exp_avg, exp_avg_stride, exp_avg_sq,
+                                      exp_avg_sq_stride, coef))
+        return r;
+    return ea_check_active(active);
 }
 
 }  // namespace nic

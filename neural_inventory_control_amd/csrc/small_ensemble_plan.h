@@ -63,7 +63,7 @@ NIC_SE_FN NicSmallEnsembleSlices small_ensemble_slices(int n_scenarios, int ldb,
 // what a request is refused for (0: accepted); small_ensemble_reason names them
 enum SmallEnsembleRefusal {
     SE_OK = 0, SE_MODELS, SE_WEIGHTS, SE_REWARDS, SE_FINAL, SE_STATES, SE_HIDDEN, SE_LOGITS, SE_SLAB_ROW, SE_SLAB, SE_GRAD, SE_SCRATCH,
-    SE_ALIGN,
+    SE_ALIGN, SE_ACTIVE,
 };
 NIC_SE_FN const char* small_ensemble_reason(int r) {
     switch (r) {
@@ -80,6 +80,7 @@ NIC_SE_FN const char* small_ensemble_reason(int r) {
         case SE_GRAD: return "grad stride shorter than the columns";
         case SE_SCRATCH: return "scratch stride shorter than the reduction's scratch";
         case SE_ALIGN: return "the strides of the rewards and the histories must be multiples of 4 floats";
+        case SE_ACTIVE: return "the active mask must be NULL or 4-byte aligned";
         default: return "?";
     }
 }
@@ -127,6 +128,14 @@ NIC_SE_FN int small_ensemble_check_reduce(const NicSmallEnsemble& e, bool with_s
     return SE_OK;
 }
 
+// ---- the active-model mask (nic_small_rollout_*_active) ---------------------------------------------------------------------------
+// `active`: int32 [n_models] on the device, non-zero = the model runs; NULL = every model runs.  A workgroup of a model whose
+// entry is zero returns before its first load or store, so no byte of that model's slices is read or written.  The mask's CONTENTS
+// are device memory the host cannot read before the launch: what a request can be refused for is its address alone.
+NIC_SE_FN int small_ensemble_check_active(const void* active) { return ((uintptr_t)active & 3) == 0 ? SE_OK : SE_ACTIVE; }
+// what every K-model kernel asks at entry (m: its grid row; one scalar load and a branch)
+NIC_SE_FN bool small_ensemble_model_runs(const int32_t* active, uint32_t m) { return active == nullptr || active[m] != 0; }
+
 // ---- I problem instances (nic_small_rollout_instances_*) --------------------------------------------------------------------------
 // The K models are I instances x R replicas: model m (grid y, as in every ensemble launch) reads instance m / R's demand trace,
 // initial state and tables, each `instance x stride` floats behind instance 0's (stride 0: shared).  The kernels get m / R from one
@@ -154,8 +163,10 @@ NIC_SE_FN const char* small_instance_table_name(int k) {
     const char* n[kSiTables] = {"underage", "holding", "lead", "wh_holding", "wh_lead", "wh_edge", "ech_holding", "ech_lead"};
     return n[k];
 }
-// the descriptor's eight tables <- instance `instance`'s (a NULL table has stride 0: it stays NULL)
-NIC_SE_FN void small_instance_tables(NicSmallRolloutDesc& d, const NicSmallInstances& in, uint32_t instance) {
+// the descriptor's eight tables <- instance `instance`'s (a NULL table has stride 0: it stays NULL); Strides: NicSmallInstances, or
+// the kernels' view of one (the same ten strides)
+template <class Strides>
+NIC_SE_FN void small_instance_tables(NicSmallRolloutDesc& d, const Strides& in, uint32_t instance) {
     d.underage.p += small_instance_offset(instance, in.underage);
     d.holding.p += small_instance_offset(instance, in.holding);
     d.lead.p += small_instance_offset(instance, in.lead);

@@ -32,8 +32,10 @@ __device__ __forceinline__ float block_sum(float v, float* lds) {
 
 __global__ __launch_bounds__(kT) void sr_reduce_stage1(const float* __restrict__ slab, int n_rows, int64_t stride, int P, int cc, int rg,
                                                        int rows_per_group, const float* __restrict__ rewards, int64_t n4,
-                                                       int64_t ignore4, int nb, float* __restrict__ scratch, MStrides ms) {
+                                                       int64_t ignore4, int nb, float* __restrict__ scratch, MStrides ms,
+                                                       const int32_t* __restrict__ active) {
     __shared__ float lds[kT];
+    if (!nic::small_ensemble_model_runs(active, blockIdx.y)) return;   // (a stopped model: wave-uniform, ahead of every access)
     {
         const int64_t m = blockIdx.y;
         if (slab) slab += m * ms.slab;
@@ -87,8 +89,10 @@ __global__ __launch_bounds__(kT) void sr_reduce_stage1(const float* __restrict__
 // Stage 2: workgroup b < ceil(P / 64) owns 64 columns; its four wavefronts each add every fourth row group (independent loads in
 // flight), wavefront 0 adds the four partial sums in order.  The last workgroup adds the cost partials.
 __global__ __launch_bounds__(kT) void sr_reduce_stage2(const float* __restrict__ scratch, int P, int cc, int rg, int nb, int col_blocks,
-                                                       float* __restrict__ grad, float* __restrict__ totals, MStrides ms) {
+                                                       float* __restrict__ grad, float* __restrict__ totals, MStrides ms,
+                                                       const int32_t* __restrict__ active) {
     __shared__ float lds[kT];
+    if (!nic::small_ensemble_model_runs(active, blockIdx.y)) return;
     {
         const int64_t m = blockIdx.y;
         scratch += m * ms.scratch;
@@ -127,17 +131,18 @@ __global__ __launch_bounds__(kT) void sr_reduce_stage2(const float* __restrict__
 }
 int launch_reduce(const float* slab, int32_t n_rows, int64_t slab_stride, int32_t P, float* grad, const float* rewards,
                   int64_t n_reward_elems, int64_t ignore_elems, float* totals, float* scratch, int n_models, MStrides ms, void* stream,
-                  const char* who) {
+                  const char* who, const int32_t* active = nullptr, bool masked = false) {
     const Plan p = plan_for(slab ? n_rows : 0, slab ? P : 0, rewards ? n_reward_elems : 0);
     hipStream_t s = nic::as_stream(stream);
-    if (n_models > 0) nic::note_kernelf("sr_reduce_stage1+2<%d,%d,%d,models=%d>", p.cc, p.rg, p.nb, n_models);
+    if (masked) nic::note_kernelf("sr_reduce_stage1+2<%d,%d,%d,models=%d,active>", p.cc, p.rg, p.nb, n_models);
+    else if (n_models > 0) nic::note_kernelf("sr_reduce_stage1+2<%d,%d,%d,models=%d>", p.cc, p.rg, p.nb, n_models);
     else nic::note_kernelf("sr_reduce_stage1+2<%d,%d,%d>", p.cc, p.rg, p.nb);
     const unsigned gy = n_models > 0 ? n_models : 1;
     hipLaunchKernelGGL(sr_reduce_stage1, dim3(p.cc * p.rg + p.nb, gy), dim3(kT), 0, s, slab, n_rows, slab_stride, P, p.cc, p.rg,
-                       p.rows_per_group, rewards, n_reward_elems / 4, ignore_elems / 4, p.nb, scratch, ms);
+                       p.rows_per_group, rewards, n_reward_elems / 4, ignore_elems / 4, p.nb, scratch, ms, active);
     const int col_blocks = p.cc ? (P + 63) / 64 : 0;
     hipLaunchKernelGGL(sr_reduce_stage2, dim3(col_blocks + (p.nb ? 1 : 0), gy), dim3(kT), 0, s, scratch, P, p.cc, p.rg, p.nb, col_blocks,
-                       grad, totals, ms);
+                       grad, totals, ms, active);
     return nic::check_launch(who);
 }
 
@@ -172,17 +177,31 @@ int nic_small_rollout_reduce(const float* slab, int32_t n_rows, int64_t slab_str
                          stream, "nic_small_rollout_reduce");
 }
 
+static int ensemble_reduce(const char* who, const NicSmallEnsemble* e, const float* slab, int32_t n_rows, int64_t slab_row_stride, int32_t P,
+                           float* grad, const float* rewards, int64_t n_reward_elems, int64_t ignore_elems, float* totals, float* scratch,
+                           const int32_t* active, bool masked, void* stream) {
+    NIC_REQUIRE(e != nullptr, "%s: null ensemble", who);
+    if (int r = check_args(who, slab, n_rows, slab_row_stride, P, grad, rewards, n_reward_elems, ignore_elems, totals, scratch)) return r;
+    int why = nic::small_ensemble_check_reduce(*e, slab != nullptr, n_rows, slab_row_stride, P, rewards != nullptr, n_reward_elems);
+    if (why == 0 && masked) why = nic::small_ensemble_check_active(active);
+    NIC_REQUIRE(why == 0, "%s: %s (%d models)", who, nic::small_ensemble_reason(why), e->n_models);
+    return launch_reduce(slab, n_rows, slab_row_stride, P, grad, rewards, n_reward_elems, ignore_elems, totals, scratch, e->n_models,
+                         MStrides{e->slab, e->rewards, e->scratch, e->grad}, stream, who, active, masked);
+}
+
 int nic_small_rollout_ensemble_reduce(const NicSmallEnsemble* e, const float* slab, int32_t n_rows, int64_t slab_row_stride, int32_t P,
                                       float* grad, const float* rewards, int64_t n_reward_elems, int64_t ignore_elems, float* totals,
                                       float* scratch, void* stream) {
-    NIC_REQUIRE(e != nullptr, "nic_small_rollout_ensemble_reduce: null ensemble");
-    if (int r = check_args("nic_small_rollout_ensemble_reduce", slab, n_rows, slab_row_stride, P, grad, rewards, n_reward_elems, ignore_elems,
-                           totals, scratch))
-        return r;
-    const int why = nic::small_ensemble_check_reduce(*e, slab != nullptr, n_rows, slab_row_stride, P, rewards != nullptr, n_reward_elems);
-    NIC_REQUIRE(why == 0, "nic_small_rollout_ensemble_reduce: %s (%d models)", nic::small_ensemble_reason(why), e->n_models);
-    return launch_reduce(slab, n_rows, slab_row_stride, P, grad, rewards, n_reward_elems, ignore_elems, totals, scratch, e->n_models,
-                         MStrides{e->slab, e->rewards, e->scratch, e->grad}, stream, "nic_small_rollout_ensemble_reduce");
+    return ensemble_reduce("nic_small_rollout_ensemble_reduce", e, slab, n_rows, slab_row_stride, P, grad, rewards, n_reward_elems,
+                           ignore_elems, totals, scratch, nullptr, false, stream);
+}
+
+/* under the active-model mask: a model whose entry is zero keeps its grad row, its totals and its scratch as they are */
+int nic_small_rollout_ensemble_reduce_active(const NicSmallEnsemble* e, const float* slab, int32_t n_rows, int64_t slab_row_stride, int32_t P,
+                                             float* grad, const float* rewards, int64_t n_reward_elems, int64_t ignore_elems,
+                                             float* totals, float* scratch, const int32_t* active, void* stream) {
+    return ensemble_reduce("nic_small_rollout_ensemble_reduce_active", e, slab, n_rows, slab_row_stride, P, grad, rewards, n_reward_elems,
+                           ignore_elems, totals, scratch, active, true, stream);
 }
 
 }  // extern "C"

@@ -41,8 +41,10 @@ __device__ __forceinline__ void elu16(const f32x16& z, float (&out)[16]) {
 // from the base, with the single-model layout inside; demand, state0 and the eight tables are its instance's, instance x the stride
 // of `es.inst` from the descriptor's, instance = m / replicas by a multiply and shift (all strides zero: one batch shared by all
 // models; csrc/small_ensemble_plan.h holds the rule).  The offsets are scalar arithmetic on the kernel arguments at entry; the period loop is the single-model one.  ENS = false
-// is the single-model kernel as it was (`es` is not read).
-template <int NL, int SHAPE, bool ENS>
+// is the single-model kernel as it was (`es` is not read).  MASKED (with ENS, the *_active entry points): the same kernel behind a test of
+// the active-model mask - a workgroup of a model whose entry is zero returns at entry (small_rollout16.h says why these are
+// instantiations of their own).
+template <int NL, int SHAPE, bool ENS, bool MASKED = false>
 __global__ __launch_bounds__(64) void small_rollout_fwd_mfma_kernel(NicSmallRolloutDesc d, const float* __restrict__ weights,
                                                                     const float* __restrict__ demand,
                                                                     const float* __restrict__ state0, float* __restrict__ rewards,
@@ -51,6 +53,9 @@ __global__ __launch_bounds__(64) void small_rollout_fwd_mfma_kernel(NicSmallRoll
                                                                     nic::SrKernelStrides<nic::SrFwdStrides, ENS> es) {
     using namespace nic;
     if constexpr (ENS) {
+        if constexpr (MASKED) {   // a stopped model: one scalar load and a branch, ahead of every load, store and pointer advance
+            if (!small_ensemble_model_runs(es.inst.active, blockIdx.y)) return;
+        }
         const int64_t m = blockIdx.y;
         const uint32_t inst = small_instance_of(blockIdx.y, es.magic);
         weights += m * es.weights;
@@ -181,7 +186,7 @@ __global__ __launch_bounds__(64) void small_rollout_fwd_mfma_kernel(NicSmallRoll
 // latency-bound dH chain, whose bubbles they fill).  No dz history is written (97 rows x T x ldb x 4 B for cfg2) or read back.
 // At the end the wavefront stores its partial gradient, in the layout of the packed weights, to `slab[blockIdx.x]`.
 // ENS (with WG only): model m on its own slices and its instance's demand and tables, as in the forward kernel; g_reward is shared.
-template <int NL, bool WG, int SHAPE, bool ENS>
+template <int NL, bool WG, int SHAPE, bool ENS, bool MASKED = false>
 __global__ __launch_bounds__(64) void small_rollout_bwd_mfma_kernel(NicSmallRolloutDesc d, const float* __restrict__ weights,
                                                                     const float* __restrict__ demand,
                                                                     const float* __restrict__ states_hist,
@@ -192,6 +197,9 @@ __global__ __launch_bounds__(64) void small_rollout_bwd_mfma_kernel(NicSmallRoll
     using namespace nic;
     static_assert(WG || !ENS, "the dz-history sweep is single-model");
     if constexpr (ENS) {
+        if constexpr (MASKED) {   // a stopped model: one scalar load and a branch, ahead of every load, store and pointer advance
+            if (!small_ensemble_model_runs(es.inst.active, blockIdx.y)) return;
+        }
         const int64_t m = blockIdx.y;
         const uint32_t inst = small_instance_of(blockIdx.y, es.magic);
         weights += m * es.weights;
@@ -455,19 +463,26 @@ int validate(const NicSmallRolloutDesc* d, const char* who) {
 
 // The launches behind the entry points: grid and strides, the recorded name, then the instantiation small_rollout_variants.h picks.
 // e == nullptr is one model (the single-model instantiations, grid y = 1, no strides), else one grid row per model; inst: the problem
-// instances of nic_small_rollout_instances_* (nullptr: one, shared by all models).
-int launch_fwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst, float* rewards, float* state_final, float* states_hist,
+// instances of nic_small_rollout_instances_* (nullptr: one, shared by all models); mask: the *_active entry points' (nullptr: the others).
+int launch_fwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst, const nic::SrActive* mask, float* rewards, float* state_final, float* states_hist,
                float* hidden_hist, float* logits_hist, hipStream_t s, const char* who) {
     using namespace nic;
     const int shape = sr_shape_of(*d);
     bool launched;
     if (sr_lane_width(*d) == 16) {
-        launched = small_rollout16_fwd(*d, shape, rewards, state_final, states_hist, hidden_hist, logits_hist, s, e, inst);
+        launched = small_rollout16_fwd(*d, shape, rewards, state_final, states_hist, hidden_hist, logits_hist, s, e, inst, mask);
     } else {   // matrix-core form: 32 scenarios per wavefront
         const dim3 g32(ceil_div(d->n_scenarios, 32), e ? e->n_models : 1), b64(64);
-        const auto es = sr_with_instances(sr_fwd_strides(e, states_hist != nullptr), e, inst);   // (the kernels add m x stride unconditionally)
-        sr_note_kernel(SR_FWD, *d, shape, e, inst);
+        const auto es = sr_with_instances(sr_fwd_strides(e, states_hist != nullptr), e, inst, mask ? mask->active : nullptr);   // (the kernels add m x stride unconditionally)
+        sr_note_kernel(SR_FWD, *d, shape, e, inst, mask != nullptr);
         launched = sr_dispatch<SR_FWD>(sr_variant(SR_FWD, shape, d->n_hidden), e != nullptr, [&](auto nl, auto sh, auto ens) {
+            if constexpr (ens()) {
+                if (mask) {
+                    hipLaunchKernelGGL((small_rollout_fwd_mfma_kernel<nl(), sh(), true, true>), g32, b64, 0, s, *d, d->weights, d->demand,
+                                       d->state0, rewards, state_final, states_hist, hidden_hist, logits_hist, es);
+                    return;
+                }
+            }
             hipLaunchKernelGGL((small_rollout_fwd_mfma_kernel<nl(), sh(), ens()>), g32, b64, 0, s, *d, d->weights, d->demand, d->state0,
                                rewards, state_final, states_hist, hidden_hist, logits_hist, es);
         });
@@ -478,7 +493,7 @@ int launch_fwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const Ni
 
 // WG = true: in-kernel weight gradients into `slab` (either width, one model or K); false: the dz-history sweep (dz_hidden, dz_out)
 template <bool WG>
-int launch_bwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst, const float* states_hist, const float* hidden_hist,
+int launch_bwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst, const nic::SrActive* mask, const float* states_hist, const float* hidden_hist,
                const float* logits_hist, NicTable2 g_reward, float* dz_hidden, float* dz_out, float* slab, int64_t slab_stride,
                hipStream_t s, const char* who) {
     using namespace nic;
@@ -486,12 +501,19 @@ int launch_bwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const Ni
     const int shape = sr_shape_of(*d);
     bool launched;
     if (WG && sr_lane_width(*d) == 16) {
-        launched = small_rollout16_bwd_wgrad(*d, shape, states_hist, hidden_hist, logits_hist, g_reward, slab, slab_stride, s, e, inst);
+        launched = small_rollout16_bwd_wgrad(*d, shape, states_hist, hidden_hist, logits_hist, g_reward, slab, slab_stride, s, e, inst, mask);
     } else {
         const dim3 g32(ceil_div(d->n_scenarios, 32), e ? e->n_models : 1), b64(64);
-        const auto es = sr_with_instances(sr_bwd_strides(e), e, inst);
-        sr_note_kernel(route, *d, shape, e, inst);
+        const auto es = sr_with_instances(sr_bwd_strides(e), e, inst, mask ? mask->active : nullptr);
+        sr_note_kernel(route, *d, shape, e, inst, mask != nullptr);
         launched = sr_dispatch<route>(sr_variant(route, shape, d->n_hidden), e != nullptr, [&](auto nl, auto sh, auto ens) {
+            if constexpr (ens()) {
+                if (mask) {
+                    hipLaunchKernelGGL((small_rollout_bwd_mfma_kernel<nl(), WG, sh(), true, true>), g32, b64, 0, s, *d, d->weights, d->demand,
+                                       states_hist, hidden_hist, logits_hist, g_reward, dz_hidden, dz_out, slab, slab_stride, es);
+                    return;
+                }
+            }
             hipLaunchKernelGGL((small_rollout_bwd_mfma_kernel<nl(), WG, sh(), ens()>), g32, b64, 0, s, *d, d->weights, d->demand,
                                states_hist, hidden_hist, logits_hist, g_reward, dz_hidden, dz_out, slab, slab_stride, es);
         });
@@ -512,7 +534,7 @@ int nic_small_rollout_fwd(const NicSmallRolloutDesc* d, float* rewards, float* s
     if (int e = validate(d, "nic_small_rollout_fwd")) return e;
     NIC_REQUIRE(d->state0 && rewards && state_final, "nic_small_rollout_fwd: null buffer");
     NIC_REQUIRE(!states_hist || (hidden_hist && logits_hist), "nic_small_rollout_fwd: incomplete history buffers");
-    return launch_fwd(d, nullptr, nullptr, rewards, state_final, states_hist, hidden_hist, logits_hist, nic::as_stream(stream), "nic_small_rollout_fwd");
+    return launch_fwd(d, nullptr, nullptr, nullptr, rewards, state_final, states_hist, hidden_hist, logits_hist, nic::as_stream(stream), "nic_small_rollout_fwd");
 }
 
 /* (one partial-gradient row per wavefront; sized for the 16-scenario form - the 32-scenario form fills the first half and the
@@ -526,7 +548,7 @@ int nic_small_rollout_bwd_wgrad(const NicSmallRolloutDesc* d, const float* state
     const int n_packed = nic::sr_packed_count(d->F, d->n_hidden, d->n_out);
     NIC_REQUIRE(slab_stride >= n_packed, "nic_small_rollout_bwd_wgrad: slab rows (%lld) shorter than the packed weights (%d)",
                 (long long)slab_stride, n_packed);
-    return launch_bwd<true>(d, nullptr, nullptr, states_hist, hidden_hist, logits_hist, g_reward, nullptr, nullptr, slab, slab_stride,
+    return launch_bwd<true>(d, nullptr, nullptr, nullptr, states_hist, hidden_hist, logits_hist, g_reward, nullptr, nullptr, slab, slab_stride,
                             nic::as_stream(stream), "nic_small_rollout_bwd_wgrad");
 }
 
@@ -537,7 +559,7 @@ int nic_small_rollout_bwd(const NicSmallRolloutDesc* d, const float* states_hist
     NIC_REQUIRE(d->lane_scenarios != 16, "nic_small_rollout_bwd: the dz-history sweep reads the [row][t][ldb] history of the 32-scenario forward");
     NIC_REQUIRE(states_hist && hidden_hist && logits_hist && g_reward.p && dz_hidden && dz_out,
                 "nic_small_rollout_bwd: null buffer");
-    return launch_bwd<false>(d, nullptr, nullptr, states_hist, hidden_hist, logits_hist, g_reward, dz_hidden, dz_out, nullptr, 0,
+    return launch_bwd<false>(d, nullptr, nullptr, nullptr, states_hist, hidden_hist, logits_hist, g_reward, dz_hidden, dz_out, nullptr, 0,
                              nic::as_stream(stream), "nic_small_rollout_bwd");
 }
 
@@ -551,62 +573,109 @@ int nic_small_rollout_ensemble_slices(const NicSmallRolloutDesc* d, NicSmallEnse
     return 0;
 }
 
+// the four forward entry points (ensemble / instances, each with or without the mask) are one request: `inst` and `mask` nullptr
+// where the entry point has none
+static int ensemble_fwd(const char* who, const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst, bool with_inst,
+                        const nic::SrActive* mask, float* rewards, float* state_final, float* states_hist, float* hidden_hist,
+                        float* logits_hist, void* stream) {
+    if (int r = validate(d, who)) return r;
+    if (with_inst) NIC_REQUIRE(e != nullptr && inst != nullptr, "%s: null ensemble / instances", who);
+    else NIC_REQUIRE(e != nullptr, "%s: null ensemble", who);
+    NIC_REQUIRE(d->state0 && rewards && state_final, "%s: null buffer", who);
+    NIC_REQUIRE((states_hist != nullptr) == (hidden_hist != nullptr) && (states_hist != nullptr) == (logits_hist != nullptr),
+                "%s: incomplete history buffers", who);
+    int why = nic::small_ensemble_check_fwd(*e, slices_of(*d), states_hist != nullptr);
+    NIC_REQUIRE(why == 0, "%s: %s (%d models)", who, nic::small_ensemble_reason(why), e->n_models);
+    if (with_inst) {
+        why = nic::small_instances_check(*inst, e->n_models, *d);
+        NIC_REQUIRE(why == 0, "%s: %s (%d models, %d instances)", who, nic::small_instances_reason(why), e->n_models, inst->n_instances);
+    }
+    if (mask) {
+        why = nic::small_ensemble_check_active(mask->active);
+        NIC_REQUIRE(why == 0, "%s: %s (%d models)", who, nic::small_ensemble_reason(why), e->n_models);
+    }
+    return launch_fwd(d, e, inst, mask, rewards, state_final, states_hist, hidden_hist, logits_hist, nic::as_stream(stream), who);
+}
+
+static int ensemble_bwd_wgrad(const char* who, const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst,
+                              bool with_inst, const nic::SrActive* mask, const float* states_hist, const float* hidden_hist,
+                              const float* logits_hist, NicTable2 g_reward, float* slab, int64_t slab_row_stride, void* stream) {
+    if (int r = validate(d, who)) return r;
+    if (with_inst) NIC_REQUIRE(e != nullptr && inst != nullptr, "%s: null ensemble / instances", who);
+    else NIC_REQUIRE(e != nullptr, "%s: null ensemble", who);
+    NIC_REQUIRE(states_hist && hidden_hist && logits_hist && g_reward.p && slab, "%s: null buffer", who);
+    int why = nic::small_ensemble_check_bwd(*e, slices_of(*d), slab_row_stride);
+    NIC_REQUIRE(why == 0, "%s: %s (%d models, slab rows of %lld)", who, nic::small_ensemble_reason(why), e->n_models, (long long)slab_row_stride);
+    if (with_inst) {
+        why = nic::small_instances_check(*inst, e->n_models, *d);
+        NIC_REQUIRE(why == 0, "%s: %s (%d models, %d instances)", who, nic::small_instances_reason(why), e->n_models, inst->n_instances);
+    }
+    if (mask) {
+        why = nic::small_ensemble_check_active(mask->active);
+        NIC_REQUIRE(why == 0, "%s: %s (%d models)", who, nic::small_ensemble_reason(why), e->n_models);
+    }
+    return launch_bwd<true>(d, e, inst, mask, states_hist, hidden_hist, logits_hist, g_reward, nullptr, nullptr, slab, slab_row_stride,
+                            nic::as_stream(stream), who);
+}
+
 int nic_small_rollout_ensemble_fwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, float* rewards, float* state_final,
                                    float* states_hist, float* hidden_hist, float* logits_hist, void* stream) {
-    if (int r = validate(d, "nic_small_rollout_ensemble_fwd")) return r;
-    NIC_REQUIRE(e != nullptr, "nic_small_rollout_ensemble_fwd: null ensemble");
-    NIC_REQUIRE(d->state0 && rewards && state_final, "nic_small_rollout_ensemble_fwd: null buffer");
-    NIC_REQUIRE((states_hist != nullptr) == (hidden_hist != nullptr) && (states_hist != nullptr) == (logits_hist != nullptr),
-                "nic_small_rollout_ensemble_fwd: incomplete history buffers");
-    const int why = nic::small_ensemble_check_fwd(*e, slices_of(*d), states_hist != nullptr);
-    NIC_REQUIRE(why == 0, "nic_small_rollout_ensemble_fwd: %s (%d models)", nic::small_ensemble_reason(why), e->n_models);
-    return launch_fwd(d, e, nullptr, rewards, state_final, states_hist, hidden_hist, logits_hist, nic::as_stream(stream), "nic_small_rollout_ensemble_fwd");
+    return ensemble_fwd("nic_small_rollout_ensemble_fwd", d, e, nullptr, false, nullptr, rewards, state_final, states_hist, hidden_hist,
+                        logits_hist, stream);
 }
 
 int nic_small_rollout_ensemble_bwd_wgrad(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const float* states_hist,
                                          const float* hidden_hist, const float* logits_hist, NicTable2 g_reward, float* slab,
                                          int64_t slab_row_stride, void* stream) {
-    if (int r = validate(d, "nic_small_rollout_ensemble_bwd_wgrad")) return r;
-    NIC_REQUIRE(e != nullptr, "nic_small_rollout_ensemble_bwd_wgrad: null ensemble");
-    NIC_REQUIRE(states_hist && hidden_hist && logits_hist && g_reward.p && slab, "nic_small_rollout_ensemble_bwd_wgrad: null buffer");
-    const int why = nic::small_ensemble_check_bwd(*e, slices_of(*d), slab_row_stride);
-    NIC_REQUIRE(why == 0, "nic_small_rollout_ensemble_bwd_wgrad: %s (%d models, slab rows of %lld)", nic::small_ensemble_reason(why),
-                e->n_models, (long long)slab_row_stride);
-    return launch_bwd<true>(d, e, nullptr, states_hist, hidden_hist, logits_hist, g_reward, nullptr, nullptr, slab, slab_row_stride,
-                            nic::as_stream(stream), "nic_small_rollout_ensemble_bwd_wgrad");
+    return ensemble_bwd_wgrad("nic_small_rollout_ensemble_bwd_wgrad", d, e, nullptr, false, nullptr, states_hist, hidden_hist, logits_hist,
+                              g_reward, slab, slab_row_stride, stream);
 }
 
 /* ---- K models on I problem instances (csrc/small_ensemble_plan.h: the model -> instance rule, the offsets and the checks) ---- */
 int nic_small_rollout_instances_fwd(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst,
                                     float* rewards, float* state_final, float* states_hist, float* hidden_hist,
                                     float* logits_hist, void* stream) {
-    if (int r = validate(d, "nic_small_rollout_instances_fwd")) return r;
-    NIC_REQUIRE(e != nullptr && inst != nullptr, "nic_small_rollout_instances_fwd: null ensemble / instances");
-    NIC_REQUIRE(d->state0 && rewards && state_final, "nic_small_rollout_instances_fwd: null buffer");
-    NIC_REQUIRE((states_hist != nullptr) == (hidden_hist != nullptr) && (states_hist != nullptr) == (logits_hist != nullptr),
-                "nic_small_rollout_instances_fwd: incomplete history buffers");
-    int why = nic::small_ensemble_check_fwd(*e, slices_of(*d), states_hist != nullptr);
-    NIC_REQUIRE(why == 0, "nic_small_rollout_instances_fwd: %s (%d models)", nic::small_ensemble_reason(why), e->n_models);
-    why = nic::small_instances_check(*inst, e->n_models, *d);
-    NIC_REQUIRE(why == 0, "nic_small_rollout_instances_fwd: %s (%d models, %d instances)", nic::small_instances_reason(why), e->n_models,
-                inst->n_instances);
-    return launch_fwd(d, e, inst, rewards, state_final, states_hist, hidden_hist, logits_hist, nic::as_stream(stream),
-                      "nic_small_rollout_instances_fwd");
+    return ensemble_fwd("nic_small_rollout_instances_fwd", d, e, inst, true, nullptr, rewards, state_final, states_hist, hidden_hist,
+                        logits_hist, stream);
 }
 
 int nic_small_rollout_instances_bwd_wgrad(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst,
                                           const float* states_hist, const float* hidden_hist, const float* logits_hist,
                                           NicTable2 g_reward, float* slab, int64_t slab_row_stride, void* stream) {
-    if (int r = validate(d, "nic_small_rollout_instances_bwd_wgrad")) return r;
-    NIC_REQUIRE(e != nullptr && inst != nullptr, "nic_small_rollout_instances_bwd_wgrad: null ensemble / instances");
-    NIC_REQUIRE(states_hist && hidden_hist && logits_hist && g_reward.p && slab, "nic_small_rollout_instances_bwd_wgrad: null buffer");
-    int why = nic::small_ensemble_check_bwd(*e, slices_of(*d), slab_row_stride);
-    NIC_REQUIRE(why == 0, "nic_small_rollout_instances_bwd_wgrad: %s (%d models, slab rows of %lld)", nic::small_ensemble_reason(why),
-                e->n_models, (long long)slab_row_stride);
-    why = nic::small_instances_check(*inst, e->n_models, *d);
-    NIC_REQUIRE(why == 0, "nic_small_rollout_instances_bwd_wgrad: %s (%d models, %d instances)", nic::small_instances_reason(why),
-                e->n_models, inst->n_instances);
-    return launch_bwd<true>(d, e, inst, states_hist, hidden_hist, logits_hist, g_reward, nullptr, nullptr, slab, slab_row_stride,
-                            nic::as_stream(stream), "nic_small_rollout_instances_bwd_wgrad");
+    return ensemble_bwd_wgrad("nic_small_rollout_instances_bwd_wgrad", d, e, inst, true, nullptr, states_hist, hidden_hist, logits_hist,
+                              g_reward, slab, slab_row_stride, stream);
+}
+
+/* ---- the same four under the active-model mask (csrc/small_ensemble_plan.h): a model whose entry is zero is not run ---- */
+int nic_small_rollout_ensemble_fwd_active(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, float* rewards, float* state_final,
+                                          float* states_hist, float* hidden_hist, float* logits_hist, const int32_t* active, void* stream) {
+    const nic::SrActive mask{active};
+    return ensemble_fwd("nic_small_rollout_ensemble_fwd_active", d, e, nullptr, false, &mask, rewards, state_final, states_hist, hidden_hist,
+                        logits_hist, stream);
+}
+
+int nic_small_rollout_ensemble_bwd_wgrad_active(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const float* states_hist,
+                                                const float* hidden_hist, const float* logits_hist, NicTable2 g_reward, float* slab,
+                                                int64_t slab_row_stride, const int32_t* active, void* stream) {
+    const nic::SrActive mask{active};
+    return ensemble_bwd_wgrad("nic_small_rollout_ensemble_bwd_wgrad_active", d, e, nullptr, false, &mask, states_hist, hidden_hist,
+                              logits_hist, g_reward, slab, slab_row_stride, stream);
+}
+
+int nic_small_rollout_instances_fwd_active(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst,
+                                           float* rewards, float* state_final, float* states_hist, float* hidden_hist,
+                                           float* logits_hist, const int32_t* active, void* stream) {
+    const nic::SrActive mask{active};
+    return ensemble_fwd("nic_small_rollout_instances_fwd_active", d, e, inst, true, &mask, rewards, state_final, states_hist, hidden_hist,
+                        logits_hist, stream);
+}
+
+int nic_small_rollout_instances_bwd_wgrad_active(const NicSmallRolloutDesc* d, const NicSmallEnsemble* e, const NicSmallInstances* inst,
+                                                 const float* states_hist, const float* hidden_hist, const float* logits_hist,
+                                                 NicTable2 g_reward, float* slab, int64_t slab_row_stride, const int32_t* active,
+                                                 void* stream) {
+    const nic::SrActive mask{active};
+    return ensemble_bwd_wgrad("nic_small_rollout_instances_bwd_wgrad_active", d, e, inst, true, &mask, states_hist, hidden_hist, logits_hist,
+                              g_reward, slab, slab_row_stride, stream);
 }
 }

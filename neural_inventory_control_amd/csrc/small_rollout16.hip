@@ -74,8 +74,9 @@ __device__ __forceinline__ void layer32(const float (&aW)[2][8], const float (&b
 // own slice of every per-model buffer (m x the stride of `es`, single-model layout inside a slice) and on its instance's demand,
 // state0 and tables (instance = m / replicas x the stride of `es.inst`; all zero: shared - csrc/small_ensemble_plan.h).  The offsets are
 // wave-uniform - scalar arithmetic on the kernel arguments before the first load - and nothing in the period loop knows of them.  ENS = false is the
-// single-model kernel as it was (`es` is not read).
-template <int NL, int SHAPE, bool ENS>
+// single-model kernel as it was (`es` is not read).  MASKED (with ENS, the *_active entry points): the same kernel behind a test
+// of the active-model mask - a workgroup of a model whose entry is zero returns at entry.
+template <int NL, int SHAPE, bool ENS, bool MASKED = false>
 __global__ __launch_bounds__(64, 2) void small_rollout16_fwd_kernel(NicSmallRolloutDesc d, const float* __restrict__ weights,
                                                                     const float* __restrict__ demand,
                                                                     const float* __restrict__ state0, float* __restrict__ rewards,
@@ -84,6 +85,9 @@ __global__ __launch_bounds__(64, 2) void small_rollout16_fwd_kernel(NicSmallRoll
                                                                     nic::SrKernelStrides<nic::SrFwdStrides, ENS> es) {
     using namespace nic;
     if constexpr (ENS) {
+        if constexpr (MASKED) {   // a stopped model: one scalar load and a branch, ahead of every load, store and pointer advance
+            if (!small_ensemble_model_runs(es.inst.active, blockIdx.y)) return;
+        }
         const int64_t m = blockIdx.y;
         const uint32_t inst = small_instance_of(blockIdx.y, es.magic);
         demand += small_instance_offset(inst, es.inst.demand);
@@ -222,7 +226,7 @@ __global__ __launch_bounds__(64, 2) void small_rollout16_fwd_kernel(NicSmallRoll
 // per period and layer the pre-activation gradient and the layer input go through two wave-private LDS tiles ([32 rows][16
 // scenarios], row stride 17) into row-owner operands, and 16 MFMAs (4 output tiles x 4 steps of 4 scenarios) add dZ X^T into
 // accumulators that stay in registers for the whole horizon.
-template <int NL, int SHAPE, bool ENS>
+template <int NL, int SHAPE, bool ENS, bool MASKED = false>
 __global__ __launch_bounds__(64, 2) void small_rollout16_bwd_kernel(NicSmallRolloutDesc d, const float* __restrict__ weights,
                                                                  const float* __restrict__ demand,
                                                                  const float* __restrict__ states_hist,
@@ -231,6 +235,9 @@ __global__ __launch_bounds__(64, 2) void small_rollout16_bwd_kernel(NicSmallRoll
                                                                  float* __restrict__ slab, int64_t slab_stride, nic::SrKernelStrides<nic::SrBwdStrides, ENS> es) {
     using namespace nic;
     if constexpr (ENS) {   // (model m on its own slices and its instance's inputs, see the forward kernel; g_reward is shared)
+        if constexpr (MASKED) {   // a stopped model: one scalar load and a branch, ahead of every load, store and pointer advance
+            if (!small_ensemble_model_runs(es.inst.active, blockIdx.y)) return;
+        }
         const int64_t m = blockIdx.y;
         const uint32_t inst = small_instance_of(blockIdx.y, es.magic);
         demand += small_instance_offset(inst, es.inst.demand);
@@ -517,11 +524,19 @@ namespace nic {
 // e == nullptr: the single-model kernels (grid y = 1, no strides); else the ensemble instantiations, one grid row per model, on
 // inst's problem instances (nullptr: one, shared)
 bool small_rollout16_fwd(const NicSmallRolloutDesc& d, int shape, float* rewards, float* state_final, float* states_hist,
-                         float* hidden_hist, float* logits_hist, hipStream_t s, const NicSmallEnsemble* e, const NicSmallInstances* inst) {
+                         float* hidden_hist, float* logits_hist, hipStream_t s, const NicSmallEnsemble* e, const NicSmallInstances* inst,
+                         const SrActive* mask) {
     const dim3 grid(nic::ceil_div(d.n_scenarios, 16), e ? e->n_models : 1), block(64);
-    const auto es = sr_with_instances(sr_fwd_strides(e, states_hist != nullptr), e, inst);   // (the kernels add m x stride unconditionally)
-    sr_note_kernel(SR_FWD, d, shape, e, inst);
+    const auto es = sr_with_instances(sr_fwd_strides(e, states_hist != nullptr), e, inst, mask ? mask->active : nullptr);   // (the kernels add m x stride unconditionally)
+    sr_note_kernel(SR_FWD, d, shape, e, inst, mask != nullptr);
     return sr_dispatch<SR_FWD>(sr_variant(SR_FWD, shape, d.n_hidden), e != nullptr, [&](auto nl, auto sh, auto ens) {
+        if constexpr (ens()) {
+            if (mask) {
+                hipLaunchKernelGGL((small_rollout16_fwd_kernel<nl(), sh(), true, true>), grid, block, 0, s, d, d.weights, d.demand, d.state0,
+                                   rewards, state_final, states_hist, hidden_hist, logits_hist, es);
+                return;
+            }
+        }
         hipLaunchKernelGGL((small_rollout16_fwd_kernel<nl(), sh(), ens()>), grid, block, 0, s, d, d.weights, d.demand, d.state0, rewards,
                            state_final, states_hist, hidden_hist, logits_hist, es);
     });
@@ -529,11 +544,18 @@ bool small_rollout16_fwd(const NicSmallRolloutDesc& d, int shape, float* rewards
 
 bool small_rollout16_bwd_wgrad(const NicSmallRolloutDesc& d, int shape, const float* states_hist, const float* hidden_hist,
                                const float* logits_hist, NicTable2 g_reward, float* slab, int64_t slab_stride, hipStream_t s,
-                               const NicSmallEnsemble* e, const NicSmallInstances* inst) {
+                               const NicSmallEnsemble* e, const NicSmallInstances* inst, const SrActive* mask) {
     const dim3 grid(nic::ceil_div(d.n_scenarios, 16), e ? e->n_models : 1), block(64);
-    const auto es = sr_with_instances(sr_bwd_strides(e), e, inst);
-    sr_note_kernel(SR_BWD_WGRAD, d, shape, e, inst);
+    const auto es = sr_with_instances(sr_bwd_strides(e), e, inst, mask ? mask->active : nullptr);
+    sr_note_kernel(SR_BWD_WGRAD, d, shape, e, inst, mask != nullptr);
     return sr_dispatch<SR_BWD_WGRAD>(sr_variant(SR_BWD_WGRAD, shape, d.n_hidden), e != nullptr, [&](auto nl, auto sh, auto ens) {
+        if constexpr (ens()) {
+            if (mask) {
+                hipLaunchKernelGGL((small_rollout16_bwd_kernel<nl(), sh(), true, true>), grid, block, 0, s, d, d.weights, d.demand, states_hist,
+                                   hidden_hist, logits_hist, g_reward, slab, slab_stride, es);
+                return;
+            }
+        }
         hipLaunchKernelGGL((small_rollout16_bwd_kernel<nl(), sh(), ens()>), grid, block, 0, s, d, d.weights, d.demand, states_hist,
                            hidden_hist, logits_hist, g_reward, slab, slab_stride, es);
     });

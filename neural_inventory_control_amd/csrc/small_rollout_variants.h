@@ -3,6 +3,7 @@
 // HIP (tests/small_ensemble_plan_harness.cpp compiles it with the host compiler alone).
 #pragma once
 #include <stdio.h>
+#include <string.h>
 
 #include <type_traits>
 
@@ -44,9 +45,10 @@ constexpr SrVariant sr_variant(SrRoute route, int shape, int n_hidden) {
 
 // The recorded kernel name (nic_last_kernel()).  It states the REQUEST - width, n_hidden, the chain's shape class, the models of an
 // ensemble launch (n_models 0: the single-model entry points), the instances of a launch through nic_small_rollout_instances_*
-// (n_instances 0: every other entry point) -, so the two dz-history cells without a kernel of their own are recorded under their
+// (n_instances 0: every other entry point), `active` for a launch through the *_active entry points -, so the two dz-history cells without a kernel of their own are recorded under their
 // shape's name.
-inline void sr_kernel_name(char* out, size_t size, SrRoute route, int width, int n_hidden, int shape, int n_models, int n_instances = 0) {
+inline void sr_kernel_name(char* out, size_t size, SrRoute route, int width, int n_hidden, int shape, int n_models, int n_instances = 0,
+                           bool active = false) {
     const char* kernel = route == SR_FWD ? (width == 16 ? "small_rollout16_fwd_kernel" : "small_rollout_fwd_mfma_kernel")
                                          : (width == 16 ? "small_rollout16_bwd_kernel" : "small_rollout_bwd_mfma_kernel");
     const char* wgrad = route == SR_BWD_WGRAD ? "wgrad," : "";
@@ -54,13 +56,17 @@ inline void sr_kernel_name(char* out, size_t size, SrRoute route, int width, int
         snprintf(out, size, "%s<%d,%s%s,models=%d,instances=%d>", kernel, n_hidden, wgrad, sr_shape_name(shape), n_models, n_instances);
     else if (n_models > 0) snprintf(out, size, "%s<%d,%s%s,models=%d>", kernel, n_hidden, wgrad, sr_shape_name(shape), n_models);
     else snprintf(out, size, "%s<%d,%s%s>", kernel, n_hidden, wgrad, sr_shape_name(shape));
+    if (active) {
+        const size_t n = strlen(out);
+        if (n >= 1 && n + 8 <= size) snprintf(out + n - 1, size - n + 1, ",active>");
+    }
 }
 
 // Run-time variant -> compile-time constants: calls f(integral_constant<int, NL>, integral_constant<int, SHAPE>, bool_constant<ENS>)
 // for the cell that matches and returns true; false if the route has no such instantiation (the dz-history route has no ensemble
 // form).  f is a generic callable that launches kernel<NL, SHAPE, ENS>; it is instantiated for exactly the cells sr_variant can
 // return for ROUTE (x one model / K models where the route has both), so the set of kernels in a code object follows from
-// sr_variant and from nothing else.  (The cells are tried in the order the kernels have always had in the code objects.)
+// sr_variant and from nothing else (the launchers add, for every ENS cell, its twin that tests the active-model mask).  (The cells are tried in the order the kernels have always had in the code objects.)
 template <SrRoute ROUTE, int NL, int SHAPE, class F>
 inline bool sr_dispatch_cell(SrVariant v, bool ensemble, F& f) {
     if constexpr (sr_variant(ROUTE, SHAPE, NL).shape == SHAPE) {

@@ -79,8 +79,10 @@ class EnsembleAdam:
             self._write_max_norms(norms)
 
     # ---- one step: two launches ------------------------------------------------------------------------------------------------
-    def step(self, params, grads):
-        """params [K][>= P] (updated in place), grads [K][>= P]: float32 device tensors with contiguous rows."""
+    def step(self, params, grads, active=None):
+        """params [K][>= P] (updated in place), grads [K][>= P]: float32 device tensors with contiguous rows.  `active`: None, or
+        an int32 [K] device tensor - a model whose entry is zero sits this step out (`nic_ensemble_adam_prepare_active` /
+        `_update_active`: its counter, running products, coef / clip rows, moments and parameters keep their bits)."""
         K, P = self.n_models, self.P
         for name, t in (("params", params), ("grads", grads)):
             if not t.is_cuda:
@@ -88,6 +90,20 @@ class EnsembleAdam:
             if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != K or t.shape[1] < P or t.stride(1) != 1:
                 raise ValueError(f"EnsembleAdam.step: {name} must be float32 [{K}][>= {P}] with contiguous rows, got {tuple(t.shape)}")
         lib, stream = _lib.lib(), _lib.current_stream()
+        if active is not None:
+            if not active.is_cuda or active.dtype != torch.int32 or tuple(active.shape) != (K,) or not active.is_contiguous():
+                raise ValueError(f"EnsembleAdam.step: active must be a contiguous int32 [{K}] device tensor")
+            clipped = self.max_norm is not None
+            max_norm, clip = (self.max_norm.data_ptr(), self.clip.data_ptr()) if clipped else (None, None)
+            _lib.check(lib.nic_ensemble_adam_prepare_active(K, P, self.hyper.data_ptr(), max_norm, self.state.data_ptr(), self.coef.data_ptr(),
+                                                            grads.data_ptr() if clipped else None, _ld(grads) if clipped else 0, clip,
+                                                            active.data_ptr(), stream))
+            self.last_kernels["prepare"] = lib.nic_last_kernel().decode()
+            _lib.check(lib.nic_ensemble_adam_update_active(K, P, params.data_ptr(), _ld(params), grads.data_ptr(), _ld(grads),
+                                                           self.exp_avg.data_ptr(), _ld(self.exp_avg), self.exp_avg_sq.data_ptr(),
+                                                           _ld(self.exp_avg_sq), self.coef.data_ptr(), clip, active.data_ptr(), stream))
+            self.last_kernels["update"] = lib.nic_last_kernel().decode()
+            return
         if self.max_norm is not None:
             _lib.check(lib.nic_ensemble_adam_prepare_clipped(K, P, self.hyper.data_ptr(), self.max_norm.data_ptr(), self.state.data_ptr(),
                                                              self.coef.data_ptr(), grads.data_ptr(), _ld(grads), self.clip.data_ptr(), stream))

@@ -6,7 +6,9 @@ the bias) - `layer_slices`, `packed_count`, `grad_views`, `pack_ensemble_weights
 `EnsembleStep`, the engines' base: the one problem cache of the ensemble, materialising (policy_layers.py, in model order) and
 comparing the models' layers, `weights` and binding the models' parameters to its rows, what a step does with the
 weights before it launches (bound: nothing; bind requested: bind on the first batch; else pack, every run), the frames of `run` and
-`train_step` around an engine's `_step`, and the epoch loop `fit` / `load_best` with the best weights per model kept on the device.
+`train_step` around an engine's `_step`, the active-model mask (`active`, `set_active`: int32 [K] on the device, read by the launches
+that take one), and the epoch loop `fit` / `load_best` with the best weights per model kept on the device - with `trainer_params`,
+`Trainer.train`'s dev schedule, best-model choice and early stopping per model (`early_stopping_update`, a pure function).
 An engine provides `_step`, `run` and `train_step` with its own signatures, and sizes `grad` / `_grad_views` with its buffers.
 `check_model_list` is the part of the engines' `check_models` that does not depend on the policy."""
 import copy
@@ -158,6 +160,42 @@ def table_layouts(prob):
     return tuple((name, getattr(prob, name).scn_stride) for name in EnvProblem._TABLES if getattr(prob, name).tensor is not None)
 
 
+# ---- per-model early stopping: Trainer.train's bookkeeping (trainer.py:182-194, :547-556) on [K] tensors ------------------------------
+BEST_MODEL_CHOICES = ("dev_loss", "train_loss")
+
+
+def read_trainer_params(trainer_params):
+    """(do_dev_every_n_epochs, choose_best_model_on, early_stopping_patience_epochs or None) of a `trainer_params` dict; ValueError
+    for a value `Trainer.train` could not run with"""
+    every, choose = int(trainer_params["do_dev_every_n_epochs"]), trainer_params["choose_best_model_on"]
+    patience = trainer_params.get("early_stopping_patience_epochs", None)
+    if every < 1:
+        raise ValueError(f"do_dev_every_n_epochs must be at least 1, got {every}")
+    if choose not in BEST_MODEL_CHOICES:
+        raise ValueError(f"choose_best_model_on is one of {BEST_MODEL_CHOICES}, got {choose!r}")
+    if patience is not None and int(patience) < 0:
+        raise ValueError(f"early_stopping_patience_epochs must be None or at least 0, got {patience}")
+    return every, choose, None if patience is None else int(patience)
+
+
+def early_stopping_update(train_loss, dev_loss, best_train, best_dev, best_epoch, active, epoch, trainer_params):
+    """What `Trainer.train` does after a dev evaluation (`update_best_params_and_save`, then the patience test), for K models at
+    once: model m is better if its chosen loss (`choose_best_model_on`) is strictly below its best; a better model's best train and
+    dev loss and best epoch become this epoch's; a model stops when `epoch - best_epoch >= early_stopping_patience_epochs` (absent
+    or None: never).  Models that are not `active` change nothing.  All [K] tensors (`best_epoch` int64, `active` bool) on any
+    device, `epoch` an int; nothing is modified in place and nothing is read back.
+    Returns (better, best_train, best_dev, best_epoch, active): `better` is the mask the caller copies the weights under."""
+    _, choose, patience = read_trainer_params(trainer_params)
+    current, best = (dev_loss, best_dev) if choose == "dev_loss" else (train_loss, best_train)
+    better = (current < best) & active
+    best_train = torch.where(better, train_loss, best_train)
+    best_dev = torch.where(better, dev_loss, best_dev)
+    best_epoch = torch.where(better, torch.full_like(best_epoch, epoch), best_epoch)
+    if patience is not None:
+        active = active & ~((epoch - best_epoch) >= patience)
+    return better, best_train, best_dev, best_epoch, active
+
+
 class EnsembleStep:
     def __init__(self, models, problem_params, device):
         """`models`: what the engine's `check_models` returned"""
@@ -170,10 +208,43 @@ class EnsembleStep:
         self._bind_requested = self._bound = False
         self._dims_bound = None         # layer sizes, once the parameters are bound
         self.best_dev = self.best_weights = None   # `fit`: [K] lowest dev loss so far, [K][P] the parameters that gave it
+        # `fit(trainer_params=...)`: [K] the train loss that went with the best, the epoch of the best, the epoch a model stopped at (-1: never)
+        self.best_train = self.best_epoch = self.stopped_epoch = None
+        # the active-model mask: allocated once (a captured step keeps its address and reads its current contents); not in use -
+        # nothing launches with it - until `set_active` is given one
+        self.active = torch.ones(len(models), dtype=torch.int32, device=self.device)
+        self._masked = False
 
     @property
     def n_models(self):
         return len(self.models)
+
+    # ---- the active-model mask ----------------------------------------------------------------------------------------------------------
+    def set_active(self, mask):
+        """Which models the next runs and steps take: a length-K sequence or tensor, non-zero / True = the model runs (written into
+        `active` in place - a replayed capture follows it); None: every model, through the launches without a mask again.  An
+        inactive model's weights row, optimizer state and buffers keep their bits, and its entries of the returned totals are NaN."""
+        if mask is None:
+            self.active.fill_(1)
+            self._masked = False
+            return
+        mask = torch.as_tensor(mask)
+        if tuple(mask.shape) != (self.n_models,):
+            raise ValueError(f"{type(self).__name__}.set_active: a mask of {self.n_models} entries is expected, got {tuple(mask.shape)}")
+        self.active.copy_((mask != 0).to(device=self.device, dtype=torch.int32))
+        self._masked = True
+
+    def active_models(self):
+        """bool [K] on the host: the models the next run takes (reads the device)"""
+        return self.active.cpu() != 0
+
+    def _mask(self):
+        """what the launches get as `active`: the mask once one has been set, else None (the launches as they always were)"""
+        return self.active if self._masked else None
+
+    def _mask_totals(self, tt):
+        """NaN into the rows of a run's totals [K][2] that belong to inactive models (their launches wrote nothing there)"""
+        return tt if not self._masked else torch.where((self.active != 0)[:, None], tt, torch.full_like(tt, float("nan")))
 
     def _note(self, tag):
         name = _lib.lib().nic_last_kernel()
@@ -302,12 +373,18 @@ class EnsembleStep:
                             max_grad_norm=max_grad_norm)
 
     # ---- epochs ------------------------------------------------------------------------------------------------------------------
-    def fit(self, train_batches, dev_batches, epochs, periods, dev_periods, ignore_periods, optimizer, observation_params=None):
+    def fit(self, train_batches, dev_batches, epochs, periods, dev_periods, ignore_periods, optimizer, observation_params=None,
+            trainer_params=None):
         """`epochs` times: `train_step` over `train_batches`, then `run(train=False)` over `dev_batches` (each batch a dict, or -
         where the engine takes them - a list of I instances' dicts; the sample count is per instance).  Returns the train and dev
         histories [epochs][K]: the reported cost per (scenario, reported period, store) as `Trainer.do_one_epoch` averages it.
         The best dev loss per model and the parameters that gave it are tracked on the device (`best_dev [K]`, `best_weights
-        [K][P]`, updated with a mask): no host synchronisation inside an epoch.  `load_best()` puts them back."""
+        [K][P]`, updated with a mask): no host synchronisation inside an epoch.  `load_best()` puts them back.
+        `trainer_params` (a dict with `do_dev_every_n_epochs`, `choose_best_model_on`, optionally `early_stopping_patience_epochs`):
+        `Trainer.train`'s protocol per model instead - see `_fit_protocol`."""
+        if trainer_params is not None:
+            return self._fit_protocol(train_batches, dev_batches, epochs, periods, dev_periods, ignore_periods, optimizer,
+                                      observation_params, trainer_params)
         K, dev = self.n_models, self.device
         hist = [torch.zeros(epochs, K, device=dev), torch.zeros(epochs, K, device=dev)]
         n_stores = self.problem_params["n_stores"]
@@ -330,6 +407,61 @@ class EnsembleStep:
             better = hist[1][epoch] < self.best_dev
             self.best_dev = torch.where(better, hist[1][epoch], self.best_dev)
             self.best_weights = torch.where(better[:, None], self.weights, self.best_weights)
+        return hist[0], hist[1]
+
+    def _epoch_loss(self, batches, T, ignore_periods, optimizer, observation_params):
+        """[K] reported cost per (scenario, reported period, store) of one pass over `batches`; `optimizer`: a training pass"""
+        total, samples = torch.zeros(self.n_models, device=self.device), 0
+        for data in batches:
+            if optimizer is not None:
+                _, reported = self.train_step(data, T, ignore_periods, optimizer, observation_params)
+            else:
+                _, reported = self.run(data, T, ignore_periods, train=False, observation_params=observation_params)
+            total += reported
+            samples += (data[0] if isinstance(data, (list, tuple)) else data)["demands"].shape[0]   # (per instance)
+        if samples == 0:
+            raise ValueError(f"{type(self).__name__}.fit needs at least one training batch and one dev batch")
+        return total / float(samples * (T - ignore_periods) * self.problem_params["n_stores"])
+
+    def _fit_protocol(self, train_batches, dev_batches, epochs, periods, dev_periods, ignore_periods, optimizer, observation_params,
+                      trainer_params):
+        """`fit` as `Trainer.train` runs it (trainer.py:177-197), per model: the dev set is evaluated when `epoch %
+        do_dev_every_n_epochs == 0` (else the dev history repeats its last entry); after it, a model whose `choose_best_model_on`
+        loss is strictly below its best gets new `best_train`, `best_dev`, `best_epoch` and `best_weights` row, and a model with
+        `epoch - best_epoch >= early_stopping_patience_epochs` stops: from the next epoch on it is not in `active`, so the launches
+        that read the mask skip it and the optimizer leaves its row alone.  Starts with every model active and leaves the mask as
+        it ends.  Returns the histories [epochs][K], NaN for a model after its stop (and for every model once all have stopped and
+        the loop ended); `stopped_epoch [K]`: the epoch of the stop, -1 for none.
+        All of it is [K]-sized work on the device, nothing per batch; the one host read is per dev evaluation (only with a
+        patience), to end the loop when no model is left.  No checkpoints are written (`save_model`, `epochs_between_save`)."""
+        every, _, patience = read_trainer_params(trainer_params)
+        K, dev = self.n_models, self.device
+        nan = torch.full((K,), float("nan"), device=dev)
+        hist = [torch.full((epochs, K), float("nan"), device=dev), torch.full((epochs, K), float("nan"), device=dev)]
+        self.set_active(torch.ones(K))
+        active = torch.ones(K, dtype=torch.bool, device=dev)
+        self.best_epoch = torch.zeros(K, dtype=torch.int64, device=dev)          # (Trainer.best_epoch starts at 0)
+        self.stopped_epoch = torch.full((K,), -1, dtype=torch.int64, device=dev)
+        for epoch in range(epochs):
+            # (an engine whose launches do not read the mask still computes a stopped model's costs: they do not surface)
+            hist[0][epoch] = torch.where(active, self._epoch_loss(train_batches, periods, ignore_periods, optimizer, observation_params), nan)
+            if epoch % every != 0:
+                hist[1][epoch] = torch.where(active, hist[1][epoch - 1], nan)
+                continue
+            hist[1][epoch] = torch.where(active, self._epoch_loss(dev_batches, dev_periods, ignore_periods, None, observation_params), nan)
+            if self.best_dev is None:
+                self.best_dev = torch.full((K,), float("inf"), device=dev)
+                self.best_weights = self.weights.clone()
+            if self.best_train is None:
+                self.best_train = torch.full((K,), float("inf"), device=dev)
+            better, self.best_train, self.best_dev, self.best_epoch, still = early_stopping_update(
+                hist[0][epoch], hist[1][epoch], self.best_train, self.best_dev, self.best_epoch, active, epoch, trainer_params)
+            self.best_weights = torch.where(better[:, None], self.weights, self.best_weights)
+            self.stopped_epoch = torch.where(active & ~still, torch.full_like(self.stopped_epoch, epoch), self.stopped_epoch)
+            active = still
+            self.active.copy_(active.to(torch.int32))
+            if patience is not None and not bool(active.any()):   # (the one host read)
+                break
         return hist[0], hist[1]
 
     def load_best(self):

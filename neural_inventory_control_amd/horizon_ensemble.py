@@ -42,6 +42,11 @@ observation GEMM reads every model's own rows (`X_stride` = one model's slice; i
 model's result depends on which form ran).  The weight-gradient GEMMs, the reductions and the optimizer do not know about
 instances.  A plain dict is the one-batch path and calls `nic_horizon_rollout_ensemble_*` as before.
 
+Per-model early stopping (`fit(trainer_params=...)`, `set_active`) gets the PROTOCOL here and frozen optimizer rows only: a stopped
+model's weights row and Adam state keep their bits and its history entries are NaN, but the whole-horizon pair and the
+model-batched GEMMs still run every model - a stopped model goes on costing its share of the launches.  Skipping it there is the
+follow-up.
+
 Not part of this engine: graph replay, per-instance topology / B / horizon, Trainer / YAML / `main_run` wiring, a `torch.library`
 operator, multi-GPU sharding, bf16 GEMMs.
 """
@@ -344,8 +349,9 @@ class HorizonPolicyEnsemble(EnsembleStep):
                     ops.wgrad_reduce(slab, gw[i], gb[i], dims[i], 1.0)
                     if m == 0:
                         self._note("reduce%d" % i)
-        if optimizer is not None:
-            optimizer.step(self.weights, self.grad)
+        if optimizer is not None:   # (the one launch pair here that reads the active-model mask: a stopped model's row is frozen)
+            mask = self._mask()
+            optimizer.step(self.weights, self.grad, **({} if mask is None else {"active": mask}))
         return tt
 
     # ---- inspection helpers used by the parity tests --------------------------------------------------------------------------------

@@ -29,6 +29,12 @@ The packed-row layout, binding, the frames of `run` / `train_step`, `fit` and th
 (policy_layers.py, layout.py: no single-model engine is built here); this module has the small policies' rules, the batch
 shapes' buffers and their launch replay, the staging and the launches.
 
+Per-model early stopping: once `set_active(mask)` has been called (`fit(trainer_params=...)` does it), every launch of a step goes
+through its `_active` entry point with the engine's `active [K]`: the workgroups of a model whose entry is zero return at entry, the
+reduction and the optimizer skip its rows, so a stopped model costs no kernel time beyond its workgroups' dispatch and its weights,
+moments and buffers keep their bits; its returned totals are NaN (and with `run(train=True)` its `param.grad` keep the last values
+they had).  The grid is not shrunk to the active count.  A replayed capture holds the mask's address and reads its contents.
+
 YAML / `main_run` wiring, a `torch.library` operator and multi-GPU sharding are not part of this engine.
 """
 import torch
@@ -271,30 +277,37 @@ class SmallPolicyEnsemble(EnsembleStep, ReplayedEngine):
         else:
             fwd, bwd_wgrad, where = sr.small_rollout_instances_fwd, sr.small_rollout_instances_bwd_wgrad, (desc, sh.ens, inst)
 
+        # once a mask has been set every launch goes through its `_active` entry point (None: the launches as they always were)
+        mask = self._mask()
+        masked = {} if mask is None else {"active": mask}
+
         def launches():
-            fwd(*where, sh.rewards, sh.final, *hist)
+            fwd(*where, sh.rewards, sh.final, *hist, **masked)
             self._note("fwd")
             if train:
                 row = sh.slab.shape[2]
-                bwd_wgrad(*where, *hist, Table(sh.g_reward, 0, 1), sh.slab, row)
+                bwd_wgrad(*where, *hist, Table(sh.g_reward, 0, 1), sh.slab, row, **masked)
                 self._note("bwd")
                 sr.small_rollout_ensemble_reduce(sh.ens, sh.slab, sr.slab_rows_written(B, width), row, self.grad.shape[1], self.grad,
-                                                 sh.rewards, n_el, ignore_periods * ld, sh.totals, sh.scratch)
+                                                 sh.rewards, n_el, ignore_periods * ld, sh.totals, sh.scratch, **masked)
             else:   # the same reduction, costs only: an evaluation pass returns the very bits a training pass does
                 sr.small_rollout_ensemble_reduce(sh.ens, None, 0, 0, 0, None, sh.rewards, n_el, ignore_periods * ld, sh.totals,
-                                                 sh.scratch)
+                                                 sh.scratch, **masked)
             self._note("reduce")
             if optimizer is not None:
-                optimizer.step(self.weights, self.grad)
+                optimizer.step(self.weights, self.grad, **masked)
 
         # what a captured sequence bakes in besides this shape's buffers.  Engine-wide things are the `variant` (a change drops this
         # shape's captures now, another shape's when it is current again); the optimizer's buffers, which only a training step's
         # sequence holds, are part of the capture's key, so evaluations in between (`fit`) change nothing
         if replay.on():
-            replay.set_variant((K,) + variant + (self.small_lane_scenarios, self.weights.data_ptr(), ub))
+            replay.set_variant((K,) + variant + (self.small_lane_scenarios, self.weights.data_ptr(), ub,
+                                                 None if mask is None else mask.data_ptr()))
         opt_key = optimizer and optimizer.capture_key()   # (clipping on or off is part of it: the two run other launches)
         replay.probe_begin(train)
-        replay.call((train, opt_key, ignore_periods, shift, bool(discrete_allocation), width) + key, launches)
+        replay.call((train, opt_key, ignore_periods, shift, bool(discrete_allocation), width, mask is not None) + key, launches)
         replay.probe_end()
         replay.ran()
-        return sh.totals.clone()   # (outside the capture: the caller's tensors must not change under a later step)
+        # outside the capture: the caller's tensors must not change under a later step, and the rows of inactive models - which no
+        # launch wrote, so they hold an earlier run's values - become NaN by the mask's contents now
+        return self._mask_totals(sh.totals.clone())

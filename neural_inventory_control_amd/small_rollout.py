@@ -192,27 +192,44 @@ def ensemble_strides(n_models, **strides):
     return e
 
 
-def small_rollout_ensemble_fwd(desc, ens, rewards, state_final, states_hist, hidden_hist, logits_hist):
+# `active` in the wrappers below: None launches the entry point as it always was; an int32 [K] device tensor (non-zero: the model runs)
+# launches its `_active` twin, under which a model whose entry is zero has no byte of its slices read or written
+def _mask(active, n_models):
+    if not active.is_cuda or active.dtype != torch.int32 or tuple(active.shape) != (int(n_models),) or not active.is_contiguous():
+        raise ValueError(f"the active mask must be a contiguous int32 [{int(n_models)}] device tensor, got {active.dtype} {tuple(active.shape)}")
+    return _lib.ptr(active)
+
+
+def small_rollout_ensemble_fwd(desc, ens, rewards, state_final, states_hist, hidden_hist, logits_hist, active=None):
     ops._dev(rewards)
-    _lib.check(_lib.lib().nic_small_rollout_ensemble_fwd(desc, ens, _lib.ptr(rewards), _lib.ptr(state_final), _lib.ptr(states_hist),
-                                                         _lib.ptr(hidden_hist), _lib.ptr(logits_hist), _lib.current_stream()))
+    args = (desc, ens, _lib.ptr(rewards), _lib.ptr(state_final), _lib.ptr(states_hist), _lib.ptr(hidden_hist), _lib.ptr(logits_hist))
+    if active is None:
+        _lib.check(_lib.lib().nic_small_rollout_ensemble_fwd(*args, _lib.current_stream()))
+    else:
+        _lib.check(_lib.lib().nic_small_rollout_ensemble_fwd_active(*args, _mask(active, ens.n_models), _lib.current_stream()))
 
 
-def small_rollout_ensemble_bwd_wgrad(desc, ens, states_hist, hidden_hist, logits_hist, g_reward: Table, slab, slab_row_stride):
+def small_rollout_ensemble_bwd_wgrad(desc, ens, states_hist, hidden_hist, logits_hist, g_reward: Table, slab, slab_row_stride, active=None):
     """slab [K][>= rows x slab_row_stride]: model m's wavefront w writes its partial gradient at m * ens.slab + w * slab_row_stride."""
     ops._dev(slab)
-    _lib.check(_lib.lib().nic_small_rollout_ensemble_bwd_wgrad(desc, ens, _lib.ptr(states_hist), _lib.ptr(hidden_hist),
-                                                               _lib.ptr(logits_hist), g_reward.t2(), _lib.ptr(slab),
-                                                               int(slab_row_stride), _lib.current_stream()))
+    args = (desc, ens, _lib.ptr(states_hist), _lib.ptr(hidden_hist), _lib.ptr(logits_hist), g_reward.t2(), _lib.ptr(slab), int(slab_row_stride))
+    if active is None:
+        _lib.check(_lib.lib().nic_small_rollout_ensemble_bwd_wgrad(*args, _lib.current_stream()))
+    else:
+        _lib.check(_lib.lib().nic_small_rollout_ensemble_bwd_wgrad_active(*args, _mask(active, ens.n_models), _lib.current_stream()))
 
 
-def small_rollout_ensemble_reduce(ens, slab, n_rows, slab_row_stride, P, grad, rewards, n_reward_elems, ignore_elems, totals, scratch):
+def small_rollout_ensemble_reduce(ens, slab, n_rows, slab_row_stride, P, grad, rewards, n_reward_elems, ignore_elems, totals, scratch,
+                                  active=None):
     """grad [K][ens.grad] <- column sums of every model's first n_rows slab rows; totals [K][2] <- every model's total / reported
     cost: `nic_small_rollout_reduce` for all K models in its two launches.  Either pair may be None."""
     ops._dev(scratch)
-    _lib.check(_lib.lib().nic_small_rollout_ensemble_reduce(ens, _lib.ptr(slab), int(n_rows), int(slab_row_stride), int(P), _lib.ptr(grad),
-                                                            _lib.ptr(rewards), int(n_reward_elems), int(ignore_elems),
-                                                            _lib.ptr(totals), _lib.ptr(scratch), _lib.current_stream()))
+    args = (ens, _lib.ptr(slab), int(n_rows), int(slab_row_stride), int(P), _lib.ptr(grad), _lib.ptr(rewards), int(n_reward_elems),
+            int(ignore_elems), _lib.ptr(totals), _lib.ptr(scratch))
+    if active is None:
+        _lib.check(_lib.lib().nic_small_rollout_ensemble_reduce(*args, _lib.current_stream()))
+    else:
+        _lib.check(_lib.lib().nic_small_rollout_ensemble_reduce_active(*args, _mask(active, ens.n_models), _lib.current_stream()))
 
 
 # ---- K models on I problem instances (nic_small_rollout_instances_*, csrc/small_ensemble_plan.h) -------------------------------------
@@ -231,15 +248,22 @@ def instance_strides(n_instances, **strides):
     return inst
 
 
-def small_rollout_instances_fwd(desc, ens, inst, rewards, state_final, states_hist, hidden_hist, logits_hist):
+def small_rollout_instances_fwd(desc, ens, inst, rewards, state_final, states_hist, hidden_hist, logits_hist, active=None):
     """`small_rollout_ensemble_fwd` with every model on its instance's inputs; `desc` points at instance 0's."""
     ops._dev(rewards)
-    _lib.check(_lib.lib().nic_small_rollout_instances_fwd(desc, ens, inst, _lib.ptr(rewards), _lib.ptr(state_final), _lib.ptr(states_hist),
-                                                          _lib.ptr(hidden_hist), _lib.ptr(logits_hist), _lib.current_stream()))
+    args = (desc, ens, inst, _lib.ptr(rewards), _lib.ptr(state_final), _lib.ptr(states_hist), _lib.ptr(hidden_hist), _lib.ptr(logits_hist))
+    if active is None:
+        _lib.check(_lib.lib().nic_small_rollout_instances_fwd(*args, _lib.current_stream()))
+    else:
+        _lib.check(_lib.lib().nic_small_rollout_instances_fwd_active(*args, _mask(active, ens.n_models), _lib.current_stream()))
 
 
-def small_rollout_instances_bwd_wgrad(desc, ens, inst, states_hist, hidden_hist, logits_hist, g_reward: Table, slab, slab_row_stride):
+def small_rollout_instances_bwd_wgrad(desc, ens, inst, states_hist, hidden_hist, logits_hist, g_reward: Table, slab, slab_row_stride,
+                                      active=None):
     ops._dev(slab)
-    _lib.check(_lib.lib().nic_small_rollout_instances_bwd_wgrad(desc, ens, inst, _lib.ptr(states_hist), _lib.ptr(hidden_hist),
-                                                                _lib.ptr(logits_hist), g_reward.t2(), _lib.ptr(slab),
-                                                                int(slab_row_stride), _lib.current_stream()))
+    args = (desc, ens, inst, _lib.ptr(states_hist), _lib.ptr(hidden_hist), _lib.ptr(logits_hist), g_reward.t2(), _lib.ptr(slab),
+            int(slab_row_stride))
+    if active is None:
+        _lib.check(_lib.lib().nic_small_rollout_instances_bwd_wgrad(*args, _lib.current_stream()))
+    else:
+        _lib.check(_lib.lib().nic_small_rollout_instances_bwd_wgrad_active(*args, _mask(active, ens.n_models), _lib.current_stream()))
