@@ -533,7 +533,8 @@ int nic_small_rollout_fwd(const NicSmallRolloutDesc* d, float* rewards, float* s
                           float* hidden_hist, float* logits_hist, void* stream) {
     if (int e = validate(d, "nic_small_rollout_fwd")) return e;
     NIC_REQUIRE(d->state0 && rewards && state_final, "nic_small_rollout_fwd: null buffer");
-    NIC_REQUIRE(!states_hist || (hidden_hist && logits_hist), "nic_small_rollout_fwd: incomplete history buffers");
+    NIC_REQUIRE((states_hist != nullptr) == (hidden_hist != nullptr) && (states_hist != nullptr) == (logits_hist != nullptr),
+                "nic_small_rollout_fwd: incomplete history buffers");
     return launch_fwd(d, nullptr, nullptr, nullptr, rewards, state_final, states_hist, hidden_hist, logits_hist, nic::as_stream(stream), "nic_small_rollout_fwd");
 }
 
