@@ -13,7 +13,10 @@
 //   * general covariance (Cholesky factor L): z[0..S) kept in registers, rows of L staged in LDS once per workgroup and
 //     read as wave-uniform broadcasts; S (S + 1) / 2 FMAs per lane;
 //   * Poisson: one uniform per output, inversion by search in a per-store CDF table built once per workgroup in LDS
-//     (no expf / divide per sample).
+//     (no expf / divide per sample).  Right for means up to 80 (ops.SAMPLER_POISSON_MAX_MEAN; tested at 0.05 .. 80 draw for
+//     draw against the exact float64 quantile, tests/test_gpu_sampler_exact.py): the float32 recurrence starts at expf(-mean),
+//     which leaves the normal float32 range near 87 and is 0 above 103, where the table would be all zeros.  The kernel
+//     does not look at the means; callers that have them on the host reject larger ones (Scenario raises ValueError).
 // The generator itself is the floor: a Philox4x32-10 block is 20 32x32->64-bit multiplies (quarter-rate on the VALU) for 4
 // outputs, and Box-Muller adds a log, a sqrt and a sin/cos pair per 2 normals on the transcendental unit.
 #include "nic_common.h"
@@ -201,8 +204,12 @@ __global__ __launch_bounds__(kBlock) void sample_poisson_kernel(float* __restric
         for (int q = 0; q < 4; ++q) {
             const int s = blk * 4 + q;
             if (s < S) {
-                const float u = u01(bits[q]);
                 const float* c = cdf + s * kCdf;
+                // u01 reaches 1.0f (x >= 0xFFFFFF80) while the float32 CDF stops growing a few steps below it (lambda = 5:
+                // 1 - 3 * 2^-24): a draw above everything the CDF reaches is the first k at which the CDF is at its top, not
+                // a search to the cap.  Draws at or below the top compare exactly as before.
+                const bool flat = c[kCdf - 1] == c[kCdf - 2];   // the table ends saturated: nothing lies beyond it
+                const float u = flat ? fminf(u01(bits[q]), c[kCdf - 1]) : u01(bits[q]);
                 int k = 0;
                 while (k < kCdf - 1 && u > c[k]) ++k;  // same comparison sequence as sequential inversion
                 float extra = 0.f;
@@ -211,9 +218,11 @@ __global__ __launch_bounds__(kBlock) void sample_poisson_kernel(float* __restric
                     float F = c[k], p = c[k] - c[k - 1];
                     int kk = k;
                     while (u > F && kk < 1000) {
+                        p *= lam / (float)(kk + 1);
+                        const float Fn = F + p;
+                        if (Fn == F) break;   // the continuation has saturated below u: kk is where it reached its top
                         ++kk;
-                        p *= lam / (float)kk;
-                        F += p;
+                        F = Fn;
                     }
                     extra = (float)(kk - k);
                 }

@@ -188,6 +188,10 @@ class Scenario:
         clip = bool(demand_params["clip"])
         mark = (lambda i: events[i].record()) if events is not None else (lambda i: None)
         if demand_params["distribution"] == "poisson":
+            largest = float(np.max(np.asarray(demand_params["mean"], dtype=np.float64)))
+            if not largest <= ops.SAMPLER_POISSON_MAX_MEAN:
+                raise ValueError(f"the HIP sampler draws Poisson demand for means up to {ops.SAMPLER_POISSON_MAX_MEAN:g} "
+                                 f"(got {largest:g}); use sampler=\"numpy\" for larger ones")
             mark(0)
             ops.sample_demand(out, T, S, N, self.scenario_offset, int(seed), 1, mean, None, clip)
         else:

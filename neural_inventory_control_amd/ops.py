@@ -814,8 +814,14 @@ def segment_sum(dst, src, offsets, items, dst_scale=None, accumulate=False):
 
 # ---- sampler / utilities ---------------------------------------------------------------------------------------
 
+SAMPLER_POISSON_MAX_MEAN = 80.0   # csrc/sampler.hip: the float32 recurrence starts at expf(-mean), which has to stay a normal float
+
+
 def sample_demand(out, T, S, n_scenarios, scenario_offset, seed, kind, mean, chol, clip):
-    """out: [T][S][ldb] device tensor; kind 0 normal (chol: [S][S] lower factor), 1 poisson."""
+    """out: [T][S][ldb] device tensor; kind 0 normal (chol: [S][S] lower factor), 1 poisson.
+    Poisson means up to SAMPLER_POISSON_MAX_MEAN = 80 (the largest the kernel is tested and right for: its float32 CDF starts at
+    expf(-mean), which leaves the normal float32 range near 87 and is zero above 103, where every draw would be the search's cap);
+    the kernel itself does not look at the means, callers that have them on the host check (`Scenario` raises ValueError)."""
     _dev(out)
     check(lib().nic_sample_demand(ptr(out), T, S, n_scenarios, out.stride(1), int(scenario_offset), int(seed), kind,
                                   ptr(mean), ptr(chol), int(clip), current_stream()))
