@@ -241,6 +241,22 @@ int nic_wgrad_reduce_models(const float* slab, int64_t slab_stride, int64_t lds,
  * wgrad = 0: the forward of N x K over n_scenarios columns; wgrad = 1: the one-period weight gradient of N x K with
  * nic_wgrad_num_splits(N, K, n_scenarios) splits.  Launches nothing. */
 int nic_linear_models_ok(int32_t N, int32_t K, int32_t n_scenarios, int32_t ldb, int32_t n_models, int32_t wgrad);
+/* The three model forms under an active-model mask (per-model early stopping, trainer.py:182-194 per model): the same arguments
+ * with `active` ahead of the stream - int32 [n_models] on the device, non-zero = the model runs; NULL = every model runs.  A
+ * workgroup of a model whose entry is zero returns at entry, ahead of its pointer advance: none of that model's operands is
+ * read, none of its outputs (Y; the slab; dW, db) written.  The plan and the kernels are the unmasked call's (which passes
+ * NULL), so a model that runs gets the unmasked bits.  nic_last_kernel: the unmasked name with ",active" behind "models=K".
+ * Checks: the unmasked call's, and the mask must be NULL or 4-byte aligned (LM_MASK, csrc/linear_models_plan.h). */
+int nic_linear_fwd_models_active(const float* W, int64_t ldw, int64_t W_stride, const float* bias /* may be NULL */,
+                                 int64_t bias_stride, const float* X, int64_t X_stride, float* Y, int64_t Y_stride, int32_t N,
+                                 int32_t K, int32_t n_scenarios, int32_t ldb, int32_t act, int32_t n_models,
+                                 const int32_t* active, void* stream);
+int nic_linear_wgrad_models_active(const float* dY, int64_t dY_stride, const float* X, int64_t X_stride, float* slab,
+                                   int64_t slab_stride, int64_t lds, int32_t N, int32_t K, int32_t n_scenarios, int32_t ldb,
+                                   int32_t n_splits, int32_t n_models, const int32_t* active, void* stream);
+int nic_wgrad_reduce_models_active(const float* slab, int64_t slab_stride, int64_t lds, int32_t n_splits, float* dW, int64_t lddw,
+                                   int64_t dW_stride, float* db /* may be NULL */, int64_t db_stride, int32_t N, int32_t K,
+                                   float scale, int32_t n_models, const int32_t* active, void* stream);
 
 /* ---- policy heads (logits -> feasible orders) ------------------------------------------------------------
  * vanilla_warehouse (neural_networks.py:369-427 + apply_softmax_feasibility_function :140-166):
@@ -748,6 +764,35 @@ int nic_horizon_rollout_instances_bwd(const NicHorizonDesc* d, const NicHorizonE
                                       const float* state_hist, const float* h1_hist, const float* h2_hist,
                                       const float* logits_hist, const float* orders_hist, NicTable2 g_reward, float* dz1_hist,
                                       float* dz2_hist, float* dz3_hist, void* stream);
+
+/* ---- the four K-model launches under an active-model mask (per-model early stopping, trainer.py:182-194 per model) ----------
+ * Each is the entry point it is named after with `active` ahead of the stream: int32 [n_models] on the device, non-zero = the
+ * model runs; NULL = every model runs.  A workgroup of a model whose entry is zero returns at entry - ahead of its pointer
+ * advances, its table staging and every load, store and barrier - so NO byte of that model's slices is read or written: its
+ * rewards, final state, histories and dz buffers keep what they held.  A model that runs gets the bits of the entry point
+ * without a mask.  The test lives in instantiations of their own (MASKED), launched from here only: the kernels behind the
+ * entry points above are unchanged.  nic_last_kernel: the unmasked name with ",active" before the closing ">".
+ * Checks: the unmasked entry point's, and the mask must be NULL or 4-byte aligned (csrc/horizon_ensemble_plan.h,
+ * horizon_ensemble_check_active; its contents are device memory and cannot be checked).  A refused request returns non-zero,
+ * names its reason in nic_last_error and launches nothing.  The cost reduction under the same mask is
+ * nic_small_rollout_ensemble_reduce_active. */
+int nic_horizon_rollout_ensemble_fwd_active(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const float* z1_obs,
+                                            const float* state0, float* rewards, float* state_final, float* state_hist,
+                                            float* h1_hist, float* h2_hist, float* logits_hist, float* orders_hist,
+                                            const int32_t* active, void* stream);
+int nic_horizon_rollout_ensemble_bwd_active(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const float* state_hist,
+                                            const float* h1_hist, const float* h2_hist, const float* logits_hist,
+                                            const float* orders_hist, NicTable2 g_reward, float* dz1_hist, float* dz2_hist,
+                                            float* dz3_hist, const int32_t* active, void* stream);
+int nic_horizon_rollout_instances_fwd_active(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* inst,
+                                             const float* z1_obs, const float* state0, float* rewards, float* state_final,
+                                             float* state_hist, float* h1_hist, float* h2_hist, float* logits_hist,
+                                             float* orders_hist, const int32_t* active, void* stream);
+int nic_horizon_rollout_instances_bwd_active(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* inst,
+                                             const float* state_hist, const float* h1_hist, const float* h2_hist,
+                                             const float* logits_hist, const float* orders_hist, NicTable2 g_reward,
+                                             float* dz1_hist, float* dz2_hist, float* dz3_hist, const int32_t* active,
+                                             void* stream);
 
 /* ---- fused three-layer 32-wide MLP over gathered inputs (graph policies) -----------------------------------------
  * The GNN policy (neural_networks.py:742-1492) applies five small MLPs (`gnn.yml`: K -> 32 -> 32 -> 32 or 1, ELU inside) to

@@ -232,6 +232,10 @@ PROTOTYPES = {
     "nic_linear_wgrad_models": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "nic_wgrad_reduce_models": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _f32, _i32, _vp]),
     "nic_linear_models_ok": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    # (the three model forms with `active`, int32 [M] on the device or NULL, ahead of the stream)
+    "nic_linear_fwd_models_active": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "nic_linear_wgrad_models_active": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "nic_wgrad_reduce_models_active": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _f32, _i32, _vp, _vp]),
     "nic_head_warehouse_fwd": (C.c_int, [_vp, _vp, _vp, _f32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "nic_head_warehouse_bwd": (C.c_int, [_vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32,
                                          _i32, _vp]),
@@ -287,6 +291,17 @@ PROTOTYPES = {
     "nic_horizon_rollout_instances_bwd": (C.c_int, [C.POINTER(NicHorizonDesc), C.POINTER(NicHorizonEnsemble),
                                                     C.POINTER(NicHorizonInstances), _vp, _vp, _vp, _vp, _vp, NicTable2, _vp, _vp, _vp,
                                                     _vp]),
+    # (the four K-model launches with `active`, int32 [K] on the device or NULL, ahead of the stream)
+    "nic_horizon_rollout_ensemble_fwd_active": (C.c_int, [C.POINTER(NicHorizonDesc), C.POINTER(NicHorizonEnsemble), _vp, _vp, _vp, _vp, _vp,
+                                                          _vp, _vp, _vp, _vp, _vp, _vp]),
+    "nic_horizon_rollout_ensemble_bwd_active": (C.c_int, [C.POINTER(NicHorizonDesc), C.POINTER(NicHorizonEnsemble), _vp, _vp, _vp, _vp, _vp,
+                                                          NicTable2, _vp, _vp, _vp, _vp, _vp]),
+    "nic_horizon_rollout_instances_fwd_active": (C.c_int, [C.POINTER(NicHorizonDesc), C.POINTER(NicHorizonEnsemble),
+                                                           C.POINTER(NicHorizonInstances), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                           _vp]),
+    "nic_horizon_rollout_instances_bwd_active": (C.c_int, [C.POINTER(NicHorizonDesc), C.POINTER(NicHorizonEnsemble),
+                                                           C.POINTER(NicHorizonInstances), _vp, _vp, _vp, _vp, _vp, NicTable2, _vp, _vp,
+                                                           _vp, _vp, _vp]),
     "nic_gnn_alloc_env_fwd": (C.c_int, [_IOP, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "nic_gnn_alloc_env_bwd": (C.c_int, [_IOP, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, NicTable2, _vp, _vp, _vp, _vp, _vp]),
     "nic_gnn_period_pack_size": (C.c_int, [_i32, _i32]),

@@ -49,7 +49,7 @@ NIC_HE_FN NicHorizonEnsembleSlices horizon_ensemble_slices(const NicHorizonDesc&
 // what a request is refused for (0: accepted); horizon_ensemble_reason names them
 enum HorizonEnsembleRefusal {
     HE_OK = 0, HE_MODELS, HE_HEAD_MODE, HE_ROUND, HE_NEGATIVE, HE_W1, HE_W2, HE_W3, HE_B2, HE_B3, HE_Z1_OBS, HE_REWARDS, HE_FINAL,
-    HE_STATE_HIST, HE_H1_HIST, HE_H2_HIST, HE_LOGITS_HIST, HE_ORDERS_HIST, HE_DZ1, HE_DZ2, HE_DZ3, HE_ALIGN,
+    HE_STATE_HIST, HE_H1_HIST, HE_H2_HIST, HE_LOGITS_HIST, HE_ORDERS_HIST, HE_DZ1, HE_DZ2, HE_DZ3, HE_ALIGN, HE_ACTIVE,
 };
 NIC_HE_FN const char* horizon_ensemble_reason(int r) {
     switch (r) {
@@ -75,6 +75,7 @@ NIC_HE_FN const char* horizon_ensemble_reason(int r) {
         case HE_DZ2: return "dz2 stride shorter than its slice";
         case HE_DZ3: return "dz3 stride shorter than its slice";
         case HE_ALIGN: return "the strides of z1_obs, the rewards, the final state, the histories and the dz buffers must be multiples of 4 floats";
+        case HE_ACTIVE: return "the active mask must be NULL or 4-byte aligned";
         default: return "?";
     }
 }
@@ -134,6 +135,15 @@ NIC_HE_FN int horizon_ensemble_check_bwd(const NicHorizonDesc& d, const NicHoriz
         return HE_ALIGN;
     return HE_OK;
 }
+
+// ---- the active-model mask (nic_horizon_rollout_ensemble_*_active / _instances_*_active) ------------------------------------------
+// `active`: int32 [n_models] on the device, non-zero = the model runs; NULL = every model runs (the rule of
+// csrc/small_ensemble_plan.h, whose _active entry points take NULL too).  A workgroup of a model whose entry is zero returns before
+// its first pointer advance, load, store or barrier, so no byte of that model's slices is read or written.  The mask's CONTENTS
+// are device memory the host cannot read before the launch: what a request can be refused for is its address alone.
+NIC_HE_FN int horizon_ensemble_check_active(const void* active) { return ((uintptr_t)active & 3) == 0 ? HE_OK : HE_ACTIVE; }
+// what the MASKED kernels ask at entry (m: the grid row; one scalar load and a branch)
+NIC_HE_FN bool horizon_ensemble_model_runs(const int32_t* active, uint32_t m) { return active == nullptr || active[m] != 0; }
 
 // ---- the kernels' side: model m's pointer advance ------------------------------------------------------------------------------
 NIC_HE_FN int64_t horizon_model_offset(uint32_t model, int64_t stride) { return (int64_t)model * stride; }

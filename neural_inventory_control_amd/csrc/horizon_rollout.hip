@@ -273,9 +273,17 @@ __device__ __forceinline__ f32x4 layer64(const float (&aW)[16], const float* hx,
 // launcher), wave-uniform, so the advances stay on the scalar unit.  Shared by all instances: the mask, g_reward, everything else.
 // Demand: neither kernel reads period t0 + T (the forward's last prefetch is clamped to t0 + T - 1, the backward fetches t - 1
 // only while t > 0), so an instance's slice is (t0 + T) * S * ldb and no read reaches the next instance's trace.
-template <bool ENS> struct HzArgs;
-template <> struct HzArgs<false> { NicHorizonDesc d; };
-template <> struct HzArgs<true> { NicHorizonDesc d; NicHorizonEnsemble e; NicHorizonInstances in; uint64_t magic; };
+// The active-model mask (nic_horizon_rollout_*_active; csrc/horizon_ensemble_plan.h).  DECISION, as for the small kernels
+// (csrc/small_rollout16.h): the kernels that test the mask are instantiations of their own (MASKED, with ENS), launched by the
+// _active entry points only, and the mask pointer rides BEHIND everything HzArgs<true> holds, in HzArgs<true, true> alone - the
+// unmasked forms keep their kernel-argument bytes, their offsets and their instruction streams (DESIGN.md section 4 has the
+// comparison and the registers of the twins).
+template <bool ENS, bool MASKED = false> struct HzArgs;
+template <> struct HzArgs<false, false> { NicHorizonDesc d; };
+template <> struct HzArgs<true, false> { NicHorizonDesc d; NicHorizonEnsemble e; NicHorizonInstances in; uint64_t magic; };
+template <> struct HzArgs<true, true> { NicHorizonDesc d; NicHorizonEnsemble e; NicHorizonInstances in; uint64_t magic; const int32_t* active; };
+using HzMaskedArgs = HzArgs<true, true>;
+static_assert(offsetof(HzMaskedArgs, active) == sizeof(HzArgs<true>), "the mask rides behind the unmasked arguments");
 template <class T> __device__ __forceinline__ T* hz_model(T* p, uint32_t model, int64_t stride) {   // (NULL stays NULL: "not passed")
     return p ? p + nic::horizon_model_offset(model, stride) : p;
 }
@@ -287,12 +295,15 @@ template <class T> __device__ __forceinline__ T* hz_model(T* p, uint32_t model, 
 // nothing is waited for until the top of the next period, a whole period of the chain later.
 // (the smallest variant - one-store settings, which the reference trains in batches of 8,192 = 512 workgroups - is held to 256
 // registers so that two workgroups share a CU: one round instead of two)
-template <int MAXW, int MAXS1, bool ENS = false>
-__global__ __launch_bounds__(kThreads, (MAXS1 == 16 || HZ_FORCE_OCC2) ? 2 : 1) void horizon_fwd_kernel(HzArgs<ENS> a, const float* __restrict__ z1_obs,
+template <int MAXW, int MAXS1, bool ENS = false, bool MASKED = false>
+__global__ __launch_bounds__(kThreads, (MAXS1 == 16 || HZ_FORCE_OCC2) ? 2 : 1) void horizon_fwd_kernel(HzArgs<ENS, MASKED> a, const float* __restrict__ z1_obs,
                                                                 const float* __restrict__ state0, float* __restrict__ rewards,
                                                                 float* __restrict__ state_final, float* __restrict__ state_hist,
                                                                 float* __restrict__ h1_hist, float* __restrict__ h2_hist,
                                                                 float* __restrict__ logits_hist, float* __restrict__ orders_hist) {
+    if constexpr (MASKED) {   // a stopped model: one scalar load and a branch, ahead of every advance, load, store and barrier
+        if (!nic::horizon_ensemble_model_runs(a.active, blockIdx.y)) return;
+    }
     extern __shared__ __attribute__((aligned(16))) float lds[];
     NicHorizonDesc d = a.d;
     if constexpr (ENS) {
@@ -570,13 +581,16 @@ __global__ __launch_bounds__(kThreads, (MAXS1 == 16 || HZ_FORCE_OCC2) ? 2 : 1) v
 // the data_driven head's adjoint (per-warehouse reductions in store order between two barriers), then the three input-gradient
 // contractions on resident TRANSPOSED weight fragments - the first layer's only over the state rows (nothing else of the input
 // carries a gradient back in time).
-template <int MAXW, int VAR, bool ENS = false>
-__global__ __launch_bounds__(kThreads, (VAR == 0 || HZ_FORCE_OCC2) ? 2 : 1) void horizon_bwd_kernel(HzArgs<ENS> a, const float* __restrict__ state_hist,
+template <int MAXW, int VAR, bool ENS = false, bool MASKED = false>
+__global__ __launch_bounds__(kThreads, (VAR == 0 || HZ_FORCE_OCC2) ? 2 : 1) void horizon_bwd_kernel(HzArgs<ENS, MASKED> a, const float* __restrict__ state_hist,
                                                                 const float* __restrict__ h1_hist, const float* __restrict__ h2_hist,
                                                                 const float* __restrict__ logits_hist,
                                                                 const float* __restrict__ orders_hist, NicTable2 g_reward,
                                                                 float* __restrict__ dz1_hist, float* __restrict__ dz2_hist,
                                                                 float* __restrict__ dz3_hist) {
+    if constexpr (MASKED) {   // (a stopped model, as in the forward)
+        if (!nic::horizon_ensemble_model_runs(a.active, blockIdx.y)) return;
+    }
     constexpr int MAXT1 = VAR == 0 ? 1 : (VAR == 1 ? 3 : 4), MAXS3 = VAR == 0 ? 4 : (VAR == 1 ? 20 : 32);
     extern __shared__ __attribute__((aligned(16))) float lds[];
     NicHorizonDesc d = a.d;
@@ -869,11 +883,23 @@ HzArgs<true> hz_ensemble_args(const NicHorizonDesc* d, const NicHorizonEnsemble*
     const NicHorizonInstances one = in ? *in : nic::horizon_instances_shared();
     return HzArgs<true>{*d, *e, one, nic::horizon_instance_magic(nic::horizon_instance_replicas(e->n_models, one.n_instances))};
 }
+// the _active entry points' mask (its `active` may be NULL: every model runs); the launchers get nullptr from every other entry point
+struct HzActive { const int32_t* active; };
+HzArgs<true, true> hz_masked_args(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* in, const HzActive* mask) {
+    const HzArgs<true> a = hz_ensemble_args(d, e, in);
+    return HzArgs<true, true>{a.d, a.e, a.in, a.magic, mask->active};
+}
+// what nic_last_kernel reports for an ensemble launch: the kernel, its variant, the models, the instances (if any), `active` (if masked)
+void hz_note_ensemble(const char* kernel, int variant, const NicHorizonEnsemble* e, const NicHorizonInstances* in, bool masked) {
+    char inst[32] = "";
+    if (in) snprintf(inst, sizeof(inst), ",instances=%d", in->n_instances);
+    nic::note_kernelf("%s<8,%d,models=%d%s%s>", kernel, variant, e->n_models, inst, masked ? ",active" : "");
+}
 
 // The two launchers.  e == nullptr: the single-model kernels (grid y = 1, the descriptor alone); else the ensemble instantiations, one
 // grid row per model, after csrc/horizon_ensemble_plan.h's checks - a refused request launches nothing, and is refused before
 // anything touches the device.  in != nullptr (with e): model m reads instance m / R's demand, state0 and tables.
-int launch_fwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* in, const float* z1_obs, const float* state0,
+int launch_fwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* in, const HzActive* mask, const float* z1_obs, const float* state0,
                float* rewards, float* state_final, float* state_hist, float* h1_hist, float* h2_hist, float* logits_hist,
                float* orders_hist, void* stream) {
     if (int r = validate(d, who)) return r;
@@ -886,6 +912,8 @@ int launch_fwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsembl
         NIC_REQUIRE(why == 0, "%s: %s (%d models)", who, nic::horizon_ensemble_reason(why), e->n_models);
         const int why_in = in ? nic::horizon_instances_check(*in, e->n_models, *d) : 0;
         NIC_REQUIRE(why_in == 0, "%s: %s (%d models, %d instances)", who, nic::horizon_instances_reason(why_in), e->n_models, in->n_instances);
+        const int why_mask = mask ? nic::horizon_ensemble_check_active(mask->active) : 0;
+        NIC_REQUIRE(why_mask == 0, "%s: %s (%d models)", who, nic::horizon_ensemble_reason(why_mask), e->n_models);
     }
     const NicEnvDims& D = d->io.dims;
     const int FD = D.n_stores * D.store_slots + D.n_warehouses * D.warehouse_slots;
@@ -894,12 +922,15 @@ int launch_fwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsembl
     const dim3 grid(nic::ceil_div(D.n_scenarios, NB), e ? e->n_models : 1), block(kThreads);
     hipStream_t s = nic::as_stream(stream);
     const int steps = fwd_steps(FD);
-    if (e && in) nic::note_kernelf("horizon_fwd_kernel<8,%d,models=%d,instances=%d>", steps, e->n_models, in->n_instances);
-    else if (e) nic::note_kernelf("horizon_fwd_kernel<8,%d,models=%d>", steps, e->n_models);
+    if (e) hz_note_ensemble("horizon_fwd_kernel", steps, e, in, mask != nullptr);
     else nic::note_kernelf("horizon_fwd_kernel<8,%d>", steps);
 #define NIC_HZ_FWD(S1)                                                                                                          \
     do {                                                                                                                        \
-        if (e) {                                                                                                                \
+        if (e && mask) {                                                                                                        \
+            if (int r = allow_lds(horizon_fwd_kernel<8, S1, true, true>, bytes, who)) return r;                                 \
+            hipLaunchKernelGGL((horizon_fwd_kernel<8, S1, true, true>), grid, block, bytes, s, hz_masked_args(d, e, in, mask), z1_obs, \
+                               state0, rewards, state_final, state_hist, h1_hist, h2_hist, logits_hist, orders_hist);          \
+        } else if (e) {                                                                                                         \
             if (int r = allow_lds(horizon_fwd_kernel<8, S1, true>, bytes, who)) return r;                                       \
             hipLaunchKernelGGL((horizon_fwd_kernel<8, S1, true>), grid, block, bytes, s, hz_ensemble_args(d, e, in), z1_obs, state0, \
                                rewards, state_final, state_hist, h1_hist, h2_hist, logits_hist, orders_hist);                   \
@@ -916,7 +947,7 @@ int launch_fwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsembl
     return nic::check_launch(who);
 }
 
-int launch_bwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* in, const float* state_hist, const float* h1_hist,
+int launch_bwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* in, const HzActive* mask, const float* state_hist, const float* h1_hist,
                const float* h2_hist, const float* logits_hist, const float* orders_hist, NicTable2 g_reward, float* dz1_hist,
                float* dz2_hist, float* dz3_hist, void* stream) {
     if (int r = validate(d, who)) return r;
@@ -930,6 +961,8 @@ int launch_bwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsembl
         NIC_REQUIRE(why == 0, "%s: %s (%d models)", who, nic::horizon_ensemble_reason(why), e->n_models);
         const int why_in = in ? nic::horizon_instances_check(*in, e->n_models, *d) : 0;
         NIC_REQUIRE(why_in == 0, "%s: %s (%d models, %d instances)", who, nic::horizon_instances_reason(why_in), e->n_models, in->n_instances);
+        const int why_mask = mask ? nic::horizon_ensemble_check_active(mask->active) : 0;
+        NIC_REQUIRE(why_mask == 0, "%s: %s (%d models)", who, nic::horizon_ensemble_reason(why_mask), e->n_models);
     }
     const NicEnvDims& D = d->io.dims;
     const int FD = D.n_stores * D.store_slots + D.n_warehouses * D.warehouse_slots;
@@ -938,12 +971,15 @@ int launch_bwd(const char* who, const NicHorizonDesc* d, const NicHorizonEnsembl
     const dim3 grid(nic::ceil_div(D.n_scenarios, NB), e ? e->n_models : 1), block(kThreads);
     hipStream_t s = nic::as_stream(stream);
     const int var = bwd_variant(FD, d->n_out);
-    if (e && in) nic::note_kernelf("horizon_bwd_kernel<8,%d,models=%d,instances=%d>", var, e->n_models, in->n_instances);
-    else if (e) nic::note_kernelf("horizon_bwd_kernel<8,%d,models=%d>", var, e->n_models);
+    if (e) hz_note_ensemble("horizon_bwd_kernel", var, e, in, mask != nullptr);
     else nic::note_kernelf("horizon_bwd_kernel<8,%d>", var);
 #define NIC_HZ_BWD(V)                                                                                                           \
     do {                                                                                                                        \
-        if (e) {                                                                                                                \
+        if (e && mask) {                                                                                                        \
+            if (int r = allow_lds(horizon_bwd_kernel<8, V, true, true>, bytes, who)) return r;                                  \
+            hipLaunchKernelGGL((horizon_bwd_kernel<8, V, true, true>), grid, block, bytes, s, hz_masked_args(d, e, in, mask),   \
+                               state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward, dz1_hist, dz2_hist, dz3_hist); \
+        } else if (e) {                                                                                                         \
             if (int r = allow_lds(horizon_bwd_kernel<8, V, true>, bytes, who)) return r;                                        \
             hipLaunchKernelGGL((horizon_bwd_kernel<8, V, true>), grid, block, bytes, s, hz_ensemble_args(d, e, in), state_hist, h1_hist, \
                                h2_hist, logits_hist, orders_hist, g_reward, dz1_hist, dz2_hist, dz3_hist);                      \
@@ -979,14 +1015,14 @@ int nic_horizon_rollout_ok(const NicHorizonDesc* d) {
 int nic_horizon_rollout_fwd(const NicHorizonDesc* d, const float* z1_obs, const float* state0, float* rewards, float* state_final,
                             float* state_hist, float* h1_hist, float* h2_hist, float* logits_hist, float* orders_hist,
                             void* stream) {
-    return launch_fwd("nic_horizon_rollout_fwd", d, nullptr, nullptr, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist,
+    return launch_fwd("nic_horizon_rollout_fwd", d, nullptr, nullptr, nullptr, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist,
                       logits_hist, orders_hist, stream);
 }
 
 int nic_horizon_rollout_bwd(const NicHorizonDesc* d, const float* state_hist, const float* h1_hist, const float* h2_hist,
                             const float* logits_hist, const float* orders_hist, NicTable2 g_reward, float* dz1_hist,
                             float* dz2_hist, float* dz3_hist, void* stream) {
-    return launch_bwd("nic_horizon_rollout_bwd", d, nullptr, nullptr, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward, dz1_hist,
+    return launch_bwd("nic_horizon_rollout_bwd", d, nullptr, nullptr, nullptr, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward, dz1_hist,
                       dz2_hist, dz3_hist, stream);
 }
 
@@ -1002,7 +1038,7 @@ int nic_horizon_rollout_ensemble_fwd(const NicHorizonDesc* d, const NicHorizonEn
                                      float* rewards, float* state_final, float* state_hist, float* h1_hist, float* h2_hist,
                                      float* logits_hist, float* orders_hist, void* stream) {
     NIC_REQUIRE(e != nullptr, "nic_horizon_rollout_ensemble_fwd: null ensemble");
-    return launch_fwd("nic_horizon_rollout_ensemble_fwd", d, e, nullptr, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist,
+    return launch_fwd("nic_horizon_rollout_ensemble_fwd", d, e, nullptr, nullptr, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist,
                       logits_hist, orders_hist, stream);
 }
 
@@ -1010,7 +1046,7 @@ int nic_horizon_rollout_ensemble_bwd(const NicHorizonDesc* d, const NicHorizonEn
                                      const float* h2_hist, const float* logits_hist, const float* orders_hist, NicTable2 g_reward,
                                      float* dz1_hist, float* dz2_hist, float* dz3_hist, void* stream) {
     NIC_REQUIRE(e != nullptr, "nic_horizon_rollout_ensemble_bwd: null ensemble");
-    return launch_bwd("nic_horizon_rollout_ensemble_bwd", d, e, nullptr, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward, dz1_hist,
+    return launch_bwd("nic_horizon_rollout_ensemble_bwd", d, e, nullptr, nullptr, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward, dz1_hist,
                       dz2_hist, dz3_hist, stream);
 }
 
@@ -1019,7 +1055,7 @@ int nic_horizon_rollout_instances_fwd(const NicHorizonDesc* d, const NicHorizonE
                                       const float* z1_obs, const float* state0, float* rewards, float* state_final, float* state_hist,
                                       float* h1_hist, float* h2_hist, float* logits_hist, float* orders_hist, void* stream) {
     NIC_REQUIRE(e != nullptr && inst != nullptr, "nic_horizon_rollout_instances_fwd: null ensemble / instances");
-    return launch_fwd("nic_horizon_rollout_instances_fwd", d, e, inst, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist,
+    return launch_fwd("nic_horizon_rollout_instances_fwd", d, e, inst, nullptr, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist,
                       logits_hist, orders_hist, stream);
 }
 
@@ -1028,7 +1064,47 @@ int nic_horizon_rollout_instances_bwd(const NicHorizonDesc* d, const NicHorizonE
                                       const float* orders_hist, NicTable2 g_reward, float* dz1_hist, float* dz2_hist, float* dz3_hist,
                                       void* stream) {
     NIC_REQUIRE(e != nullptr && inst != nullptr, "nic_horizon_rollout_instances_bwd: null ensemble / instances");
-    return launch_bwd("nic_horizon_rollout_instances_bwd", d, e, inst, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward,
+    return launch_bwd("nic_horizon_rollout_instances_bwd", d, e, inst, nullptr, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward,
                       dz1_hist, dz2_hist, dz3_hist, stream);
+}
+
+/* ---- the same four under the active-model mask (csrc/horizon_ensemble_plan.h): a model whose entry is zero is not run ---- */
+int nic_horizon_rollout_ensemble_fwd_active(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const float* z1_obs, const float* state0,
+                                            float* rewards, float* state_final, float* state_hist, float* h1_hist, float* h2_hist,
+                                            float* logits_hist, float* orders_hist, const int32_t* active, void* stream) {
+    NIC_REQUIRE(e != nullptr, "nic_horizon_rollout_ensemble_fwd_active: null ensemble");
+    const HzActive mask{active};
+    return launch_fwd("nic_horizon_rollout_ensemble_fwd_active", d, e, nullptr, &mask, z1_obs, state0, rewards, state_final, state_hist,
+                      h1_hist, h2_hist, logits_hist, orders_hist, stream);
+}
+
+int nic_horizon_rollout_ensemble_bwd_active(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const float* state_hist,
+                                            const float* h1_hist, const float* h2_hist, const float* logits_hist, const float* orders_hist,
+                                            NicTable2 g_reward, float* dz1_hist, float* dz2_hist, float* dz3_hist, const int32_t* active,
+                                            void* stream) {
+    NIC_REQUIRE(e != nullptr, "nic_horizon_rollout_ensemble_bwd_active: null ensemble");
+    const HzActive mask{active};
+    return launch_bwd("nic_horizon_rollout_ensemble_bwd_active", d, e, nullptr, &mask, state_hist, h1_hist, h2_hist, logits_hist, orders_hist,
+                      g_reward, dz1_hist, dz2_hist, dz3_hist, stream);
+}
+
+int nic_horizon_rollout_instances_fwd_active(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* inst,
+                                             const float* z1_obs, const float* state0, float* rewards, float* state_final,
+                                             float* state_hist, float* h1_hist, float* h2_hist, float* logits_hist, float* orders_hist,
+                                             const int32_t* active, void* stream) {
+    NIC_REQUIRE(e != nullptr && inst != nullptr, "nic_horizon_rollout_instances_fwd_active: null ensemble / instances");
+    const HzActive mask{active};
+    return launch_fwd("nic_horizon_rollout_instances_fwd_active", d, e, inst, &mask, z1_obs, state0, rewards, state_final, state_hist,
+                      h1_hist, h2_hist, logits_hist, orders_hist, stream);
+}
+
+int nic_horizon_rollout_instances_bwd_active(const NicHorizonDesc* d, const NicHorizonEnsemble* e, const NicHorizonInstances* inst,
+                                             const float* state_hist, const float* h1_hist, const float* h2_hist, const float* logits_hist,
+                                             const float* orders_hist, NicTable2 g_reward, float* dz1_hist, float* dz2_hist,
+                                             float* dz3_hist, const int32_t* active, void* stream) {
+    NIC_REQUIRE(e != nullptr && inst != nullptr, "nic_horizon_rollout_instances_bwd_active: null ensemble / instances");
+    const HzActive mask{active};
+    return launch_bwd("nic_horizon_rollout_instances_bwd_active", d, e, inst, &mask, state_hist, h1_hist, h2_hist, logits_hist, orders_hist,
+                      g_reward, dz1_hist, dz2_hist, dz3_hist, stream);
 }
 }

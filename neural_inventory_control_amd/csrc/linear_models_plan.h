@@ -38,7 +38,8 @@ enum LinearModelsRefusal {
     LM_OK = 0, LM_MODELS, LM_NULL, LM_SIZES, LM_ACT, LM_LD, LM_POINTER_ALIGN, LM_SPLITS, LM_NEGATIVE,
     LM_Y_STRIDE, LM_SLAB_STRIDE, LM_DW_STRIDE, LM_DB_STRIDE,          // an output stride shorter than one model's slice
     LM_W_STRIDE, LM_BIAS_STRIDE, LM_X_STRIDE, LM_DY_STRIDE,           // an input stride that is neither allowed to be 0 nor >= the slice
-    LM_ALIGN, LM_PLAN, LM_REFUSAL_END
+    LM_ALIGN, LM_PLAN, LM_REFUSAL_END,                                // (the end of what a request without a mask can be refused for)
+    LM_MASK = LM_REFUSAL_END, LM_ACTIVE_REFUSAL_END                   // the _active entry points' own
 };
 NIC_LM_FN const char* linear_models_reason(int r) {
     switch (r) {
@@ -61,9 +62,17 @@ NIC_LM_FN const char* linear_models_reason(int r) {
         case LM_DY_STRIDE: return "dY stride shorter than N * ldb";
         case LM_ALIGN: return "the strides of W, X, Y, dY and the slab must be multiples of 4 floats";
         case LM_PLAN: return "the plan picks a kernel without a model form (forward: N <= 64; weight gradient: N <= 128, staged or small tiles)";
+        case LM_MASK: return "the active mask must be NULL or 4-byte aligned";
         default: return "?";
     }
 }
+
+// ---- the active-model mask (nic_linear_fwd_models_active, nic_linear_wgrad_models_active, nic_wgrad_reduce_models_active) ---------
+// `active`: int32 [n_models] on the device, non-zero = the model runs; NULL = every model runs (what the entry points without a
+// mask pass).  A workgroup of a model whose entry is zero returns before its pointer advance: no byte of that model's operands is
+// read or written.  Only the mask's address can be checked on the host (requests carry it as `active`, 0 = NULL).
+NIC_LM_FN bool lm_mask_ok(uint64_t active) { return (active & 3) == 0; }
+NIC_LM_FN bool linear_model_runs(const int32_t* active, uint32_t model) { return active == nullptr || active[model] != 0; }
 
 // ---- the kernels' side: model m's pointer advance ------------------------------------------------------------------------------
 NIC_LM_FN int64_t linear_model_offset(uint32_t model, int64_t stride) { return (int64_t)model * stride; }
@@ -73,16 +82,19 @@ struct LmFwdRequest {
     uint64_t W, bias /* may be 0 */, X, Y;
     int64_t ldw, W_stride, bias_stride, X_stride, Y_stride;
     int N, K, n_scenarios, ldb, act, n_models;
+    uint64_t active = 0;   // the mask's address (0: none)
 };
 struct LmWgradRequest {
     uint64_t dY, X, slab;
     int64_t dY_stride, X_stride, slab_stride, lds;
     int N, K, n_scenarios, ldb, n_splits, n_models;
+    uint64_t active = 0;
 };
 struct LmReduceRequest {
     uint64_t slab, dW, db /* may be 0 */;
     int64_t slab_stride, lds, lddw, dW_stride, db_stride;
     int N, K, n_splits, n_models;
+    uint64_t active = 0;
 };
 
 NIC_LM_FN bool lm_models_ok(int n_models) { return n_models >= 1 && n_models <= kLmMaxModels; }
@@ -102,6 +114,7 @@ NIC_LM_FN int linear_models_check_fwd(const LmFwdRequest& r) {
     if (r.bias && r.bias_stride < r.N) return LM_BIAS_STRIDE;
     if (r.X_stride != 0 && r.X_stride < (int64_t)r.K * r.ldb) return LM_X_STRIDE;
     if (r.W_stride % 4 != 0 || r.X_stride % 4 != 0 || r.Y_stride % 4 != 0) return LM_ALIGN;
+    if (!lm_mask_ok(r.active)) return LM_MASK;
     return LM_OK;
 }
 NIC_LM_FN int linear_models_check_wgrad(const LmWgradRequest& r) {
@@ -115,6 +128,7 @@ NIC_LM_FN int linear_models_check_wgrad(const LmWgradRequest& r) {
     if (r.dY_stride < (int64_t)r.N * r.ldb) return LM_DY_STRIDE;
     if (r.X_stride < (int64_t)r.K * r.ldb) return LM_X_STRIDE;
     if (r.dY_stride % 4 != 0 || r.X_stride % 4 != 0 || r.slab_stride % 4 != 0) return LM_ALIGN;
+    if (!lm_mask_ok(r.active)) return LM_MASK;
     return LM_OK;
 }
 NIC_LM_FN int linear_models_check_reduce(const LmReduceRequest& r) {
@@ -127,6 +141,7 @@ NIC_LM_FN int linear_models_check_reduce(const LmReduceRequest& r) {
     if (r.db && r.db_stride < r.N) return LM_DB_STRIDE;
     if (r.slab_stride < (int64_t)r.n_splits * r.N * r.lds) return LM_SLAB_STRIDE;
     if (r.slab_stride % 4 != 0) return LM_ALIGN;
+    if (!lm_mask_ok(r.active)) return LM_MASK;
     return LM_OK;
 }
 

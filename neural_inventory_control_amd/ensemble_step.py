@@ -7,7 +7,8 @@ the bias) - `layer_slices`, `packed_count`, `grad_views`, `pack_ensemble_weights
 comparing the models' layers, `weights` and binding the models' parameters to its rows, what a step does with the
 weights before it launches (bound: nothing; bind requested: bind on the first batch; else pack, every run), the frames of `run` and
 `train_step` around an engine's `_step`, the active-model mask (`active`, `set_active`: int32 [K] on the device, read by the launches
-that take one), and the epoch loop `fit` / `load_best` with the best weights per model kept on the device - with `trainer_params`,
+that take one: all of `SmallPolicyEnsemble`'s; `HorizonPolicyEnsemble`'s optimizer, and all of its launches with `skip_inactive`,
+which `fit(trainer_params=...)` switches on for its duration), and the epoch loop `fit` / `load_best` with the best weights per model kept on the device - with `trainer_params`,
 `Trainer.train`'s dev schedule, best-model choice and early stopping per model (`early_stopping_update`, a pure function).
 An engine provides `_step`, `run` and `train_step` with its own signatures, and sizes `grad` / `_grad_views` with its buffers.
 `check_model_list` is the part of the engines' `check_models` that does not depend on the policy."""
@@ -435,6 +436,19 @@ class EnsembleStep:
         All of it is [K]-sized work on the device, nothing per batch; the one host read is per dev evaluation (only with a
         patience), to end the loop when no model is left.  No checkpoints are written (`save_model`, `epochs_between_save`)."""
         every, _, patience = read_trainer_params(trainer_params)
+        if hasattr(self, "skip_inactive"):   # an engine whose launches skip the stopped models on request only: for this fit, they do
+            previous, self.skip_inactive = self.skip_inactive, True
+            try:
+                return self._protocol_epochs(train_batches, dev_batches, epochs, periods, dev_periods, ignore_periods, optimizer,
+                                             observation_params, trainer_params, every, patience)
+            finally:
+                self.skip_inactive = previous
+        return self._protocol_epochs(train_batches, dev_batches, epochs, periods, dev_periods, ignore_periods, optimizer,
+                                     observation_params, trainer_params, every, patience)
+
+    def _protocol_epochs(self, train_batches, dev_batches, epochs, periods, dev_periods, ignore_periods, optimizer, observation_params,
+                         trainer_params, every, patience):
+        """the epochs of `_fit_protocol`"""
         K, dev = self.n_models, self.device
         nan = torch.full((K,), float("nan"), device=dev)
         hist = [torch.full((epochs, K), float("nan"), device=dev), torch.full((epochs, K), float("nan"), device=dev)]
@@ -443,7 +457,7 @@ class EnsembleStep:
         self.best_epoch = torch.zeros(K, dtype=torch.int64, device=dev)          # (Trainer.best_epoch starts at 0)
         self.stopped_epoch = torch.full((K,), -1, dtype=torch.int64, device=dev)
         for epoch in range(epochs):
-            # (an engine whose launches do not read the mask still computes a stopped model's costs: they do not surface)
+            # (launches that do not read the mask still compute a stopped model's costs: they do not surface)
             hist[0][epoch] = torch.where(active, self._epoch_loss(train_batches, periods, ignore_periods, optimizer, observation_params), nan)
             if epoch % every != 0:
                 hist[1][epoch] = torch.where(active, hist[1][epoch - 1], nan)

@@ -42,10 +42,23 @@ observation GEMM reads every model's own rows (`X_stride` = one model's slice; i
 model's result depends on which form ran).  The weight-gradient GEMMs, the reductions and the optimizer do not know about
 instances.  A plain dict is the one-batch path and calls `nic_horizon_rollout_ensemble_*` as before.
 
-Per-model early stopping (`fit(trainer_params=...)`, `set_active`) gets the PROTOCOL here and frozen optimizer rows only: a stopped
-model's weights row and Adam state keep their bits and its history entries are NaN, but the whole-horizon pair and the
-model-batched GEMMs still run every model - a stopped model goes on costing its share of the launches.  Skipping it there is the
-follow-up.
+Per-model early stopping (`fit(trainer_params=...)`, `set_active`): a stopped model's weights row and Adam state keep their bits
+and its history entries are NaN.  Whether it also leaves the launches is `skip_inactive`, a plain attribute beside `model_gemms`.
+False (the default): every launch is the one it always was, whatever the mask - only the optimizer reads it, every model's costs
+are computed and the totals are finite.  True, with a mask set: every library launch of a step takes its `_active` entry point
+with the mask - the observation GEMM, the forward, the totals reduction, the backward, the three weight-gradient contractions and
+their reductions (`nic_horizon_rollout_*_active`, `nic_linear_*_models_active`, `nic_small_rollout_ensemble_reduce_active`), for a
+dict batch and for a list of instances - and the totals of the stopped models are NaN, as on `SmallPolicyEnsemble`.  The contract is
+that engine's: for a model whose entry is zero no library launch reads or writes its slices - `rewards`, `final`, the state rows
+of `X`, the four histories, `dz1..3`, `z1`, its slab, its `grad` row and `totals` row, the reduce scratch, weights, moments and
+optimizer state - and a model that runs gets the bits of the unmasked step.  True without a mask: the unmasked launches.
+`fit(trainer_params=...)` switches it on for its duration and puts the previous value back.  The per-model loop
+(`model_gemms = False`, or a shape the plan refuses) skips the stopped models on the host from `active_models()`: one host read
+per step, on that fall-back path only; the launch pair and the totals are masked either way.
+The boundary: the torch glue of a step is NOT masked.  It prepares model-independent INPUTS and SCRATCH, not results - the
+`W1obs.copy_` of the first layer's observation columns, the copy of the observation rows into the replicas' `X`, `slabs[i].zero_()`
+- and runs for all K models as before, so a stopped model's `W1obs` block, observation rows and slab are still written (with what
+they would hold anyway).  Glue that follows the mask is not built; tools/horizon_active_step.py times its share of a step.
 
 Not part of this engine: graph replay, per-instance topology / B / horizon, Trainer / YAML / `main_run` wiring, a `torch.library`
 operator, multi-GPU sharding, bf16 GEMMs.
@@ -117,6 +130,7 @@ class HorizonPolicyEnsemble(EnsembleStep):
         self.plan = self.prob = None
         self._dpad = None               # `fill_observation_rows`' window scratch
         self.model_gemms = True         # one GEMM launch for all K models where the library takes the shape; False: the per-model loop
+        self.skip_inactive = False      # True: with a mask set (`set_active`), every library launch of a step skips the stopped models
 
     def _setup(self, prob, T, train, dims, shift, instances=()):
         """`instances`: what the key of a list-of-instances batch carries besides the shape (I, the trace length, the tables'
@@ -263,6 +277,11 @@ class HorizonPolicyEnsemble(EnsembleStep):
         self._ready_weights(lins, dims, optimizer)
         Fo, n_cols = F - FD, T * ld
         batched = self.model_gemms and self._models_ok
+        # the stopped models leave the launches only on request (`skip_inactive`) and only once a mask is set; else every launch is
+        # the unmasked one.  The per-model loops then run the models that are active (one host read, on that path only)
+        mask = self._mask() if self.skip_inactive else None
+        masked = {} if mask is None else {"active": mask}
+        running = range(K) if mask is None or batched else [m for m, on in enumerate(self.active_models().tolist()) if on]
         P, sl = self.weights.shape[1], layer_slices(dims)
         if listed:
             (prob_d, demand_soa, state0), inst = self._stage_instances(datas, probs, T_total)
@@ -293,9 +312,11 @@ class HorizonPolicyEnsemble(EnsembleStep):
             self.W1obs[:, :, :Fo].copy_(self.weights[:, o:o + n * k].view(K, n, k)[:, :, FD:])
             x_obs = X[:, FD:].flatten(2) if listed else X[0, FD:].view(Fo, n_cols)
             ops.linear_fwd_models(self.W1obs[:, :, :Fo], row0[bo:bo + n], x_obs, self.z1.view(K, dims[1], n_cols),
-                                  n_cols, _lib.NIC_ACT_NONE, bias_stride=P)
+                                  n_cols, _lib.NIC_ACT_NONE, bias_stride=P, **masked)
         else:
-            for m, ls in enumerate(lins or self._linears()):
+            linears = lins or self._linears()
+            for m in running:
+                ls = linears[m]
                 self.W1obs[m, :, :Fo].copy_(ls[0].weight.detach()[:, FD:])
                 ops.linear_fwd(self.W1obs[m, :, :Fo], ls[0].bias.detach(), X[m, FD:].view(Fo, n_cols), self.z1[m].view(dims[1], n_cols),
                                n_cols, _lib.NIC_ACT_NONE)
@@ -314,42 +335,45 @@ class HorizonPolicyEnsemble(EnsembleStep):
             fwd, bwd, where = hz.horizon_ensemble_fwd, hz.horizon_ensemble_bwd, (desc, ens)
         else:
             fwd, bwd, where = hz.horizon_instances_fwd, hz.horizon_instances_bwd, (desc, ens, inst)
-        fwd(*where, self.z1, state0, self.rewards, self.final, *hist)
+        fwd(*where, self.z1, state0, self.rewards, self.final, *hist, **masked)
         self._note("fwd")
         # every model's total / reported cost: one fixed-order reduction (two launches) for all K
         sr.small_rollout_ensemble_reduce(self._reduce, None, 0, 0, 0, None, self.rewards, n_cols, ignore_periods * ld, self.totals,
-                                         self.scratch)
+                                         self.scratch, **masked)
         tt = self.totals.clone()   # (the caller's tensors must not change under a later run)
+        if mask is not None:       # (the reduction left the stopped models' rows alone: what stands there is an earlier run's)
+            tt = self._mask_totals(tt)
         if not train:
             return tt
         if grad_scale is None:
             grad_scale = 1.0 / (B * T * self.problem_params["n_stores"])
         self._g_reward_key = sr.set_g_reward(self.g_reward, B, grad_scale, self._g_reward_key)
-        bwd(*where, *hist, Table(self.g_reward, 0, 1), *self.dz)
+        bwd(*where, *hist, Table(self.g_reward, 0, 1), *self.dz, **masked)
         self._note("bwd")
         # three weight gradients per model: FusedRollout._wgrad_over_columns' launches on model m's slices
         if batched:
             for i, x in enumerate((X, self.hist[0], self.hist[1])):   # per layer, all K models: zero, contract, reduce into grad[:, ...]
                 o, n, k, bo = sl[i]
                 self.slabs[i].zero_()
-                ops.linear_wgrad_models(self.dz[i].flatten(2), x.flatten(2), self.slabs[i], n_cols)
+                ops.linear_wgrad_models(self.dz[i].flatten(2), x.flatten(2), self.slabs[i], n_cols, **masked)
                 self._note("wgrad%d" % i)
                 ops.wgrad_reduce_models(self.slabs[i], self.grad[0, o:o + n * k].view(n, k), self.grad[0, bo:bo + n], k, 1.0,
-                                        dW_stride=P, db_stride=P)
+                                        dW_stride=P, db_stride=P, **masked)
                 self._note("reduce%d" % i)
         else:
-            for m, (gw, gb) in enumerate(self._grad_views):
+            for m in running:
+                gw, gb = self._grad_views[m]
                 inputs = [X[m], self.hist[0][m], self.hist[1][m]]
                 for i, x in enumerate(inputs):
                     slab = self.slabs[i][0]
                     slab.zero_()
                     ops.linear_wgrad(self.dz[i][m].flatten(1), x.flatten(1), slab, n_cols)
-                    if m == 0:   # (the K models of a layer run the same kernel: noted once)
+                    if m == running[0]:   # (the K models of a layer run the same kernel: noted once)
                         self._note("wgrad%d" % i)
                     ops.wgrad_reduce(slab, gw[i], gb[i], dims[i], 1.0)
-                    if m == 0:
+                    if m == running[0]:
                         self._note("reduce%d" % i)
-        if optimizer is not None:   # (the one launch pair here that reads the active-model mask: a stopped model's row is frozen)
+        if optimizer is not None:   # (reads the active-model mask whatever `skip_inactive` says: a stopped model's row is frozen)
             mask = self._mask()
             optimizer.step(self.weights, self.grad, **({} if mask is None else {"active": mask}))
         return tt

@@ -98,21 +98,24 @@ def ensemble_strides(n_models, **strides):
     return e
 
 
-def horizon_ensemble_fwd(desc, ens, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist, logits_hist, orders_hist):
-    """`horizon_fwd` for ens.n_models models in one launch: `desc` and every buffer are model 0's, model m's start m x its stride behind."""
+def horizon_ensemble_fwd(desc, ens, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist, logits_hist, orders_hist,
+                         active=None):
+    """`horizon_fwd` for ens.n_models models in one launch: `desc` and every buffer are model 0's, model m's start m x its stride behind.
+    `active`: an int32 [K] device tensor - a model whose entry is zero is not run, none of its slices is read or written
+    (`nic_horizon_rollout_ensemble_fwd_active`); None: the entry point without a mask.  The same in the three calls below."""
     ops._dev(rewards)
     p = _lib.ptr
-    _lib.check(_lib.lib().nic_horizon_rollout_ensemble_fwd(desc, ens, p(z1_obs), p(state0), p(rewards), p(state_final), p(state_hist),
-                                                           p(h1_hist), p(h2_hist), p(logits_hist), p(orders_hist),
-                                                           _lib.current_stream()))
+    fn, mask = ops.masked_entry("nic_horizon_rollout_ensemble_fwd", active, ens.n_models)
+    _lib.check(fn(desc, ens, p(z1_obs), p(state0), p(rewards), p(state_final), p(state_hist), p(h1_hist), p(h2_hist), p(logits_hist),
+                  p(orders_hist), *mask, _lib.current_stream()))
 
 
-def horizon_ensemble_bwd(desc, ens, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward: Table, dz1, dz2, dz3):
+def horizon_ensemble_bwd(desc, ens, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward: Table, dz1, dz2, dz3, active=None):
     ops._dev(dz1)
     p = _lib.ptr
-    _lib.check(_lib.lib().nic_horizon_rollout_ensemble_bwd(desc, ens, p(state_hist), p(h1_hist), p(h2_hist), p(logits_hist),
-                                                           p(orders_hist), g_reward.t2(), p(dz1), p(dz2), p(dz3),
-                                                           _lib.current_stream()))
+    fn, mask = ops.masked_entry("nic_horizon_rollout_ensemble_bwd", active, ens.n_models)
+    _lib.check(fn(desc, ens, p(state_hist), p(h1_hist), p(h2_hist), p(logits_hist), p(orders_hist), g_reward.t2(), p(dz1), p(dz2), p(dz3),
+                  *mask, _lib.current_stream()))
 
 
 # ---- K models on I problem instances (nic_horizon_rollout_instances_*, csrc/horizon_ensemble_plan.h) --------------------------------
@@ -130,19 +133,21 @@ def instance_strides(n_instances, **strides):
     return inst
 
 
-def horizon_instances_fwd(desc, ens, inst, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist, logits_hist, orders_hist):
+def horizon_instances_fwd(desc, ens, inst, z1_obs, state0, rewards, state_final, state_hist, h1_hist, h2_hist, logits_hist, orders_hist,
+                          active=None):
     """`horizon_ensemble_fwd` with model m on instance m // (ens.n_models // inst.n_instances): `desc` (demand, tables) and `state0`
     are instance 0's, instance i's start i x its stride behind."""
     ops._dev(rewards)
     p = _lib.ptr
-    _lib.check(_lib.lib().nic_horizon_rollout_instances_fwd(desc, ens, inst, p(z1_obs), p(state0), p(rewards), p(state_final), p(state_hist),
-                                                            p(h1_hist), p(h2_hist), p(logits_hist), p(orders_hist),
-                                                            _lib.current_stream()))
+    fn, mask = ops.masked_entry("nic_horizon_rollout_instances_fwd", active, ens.n_models)
+    _lib.check(fn(desc, ens, inst, p(z1_obs), p(state0), p(rewards), p(state_final), p(state_hist), p(h1_hist), p(h2_hist), p(logits_hist),
+                  p(orders_hist), *mask, _lib.current_stream()))
 
 
-def horizon_instances_bwd(desc, ens, inst, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward: Table, dz1, dz2, dz3):
+def horizon_instances_bwd(desc, ens, inst, state_hist, h1_hist, h2_hist, logits_hist, orders_hist, g_reward: Table, dz1, dz2, dz3,
+                          active=None):
     ops._dev(dz1)
     p = _lib.ptr
-    _lib.check(_lib.lib().nic_horizon_rollout_instances_bwd(desc, ens, inst, p(state_hist), p(h1_hist), p(h2_hist), p(logits_hist),
-                                                            p(orders_hist), g_reward.t2(), p(dz1), p(dz2), p(dz3),
-                                                            _lib.current_stream()))
+    fn, mask = ops.masked_entry("nic_horizon_rollout_instances_bwd", active, ens.n_models)
+    _lib.check(fn(desc, ens, inst, p(state_hist), p(h1_hist), p(h2_hist), p(logits_hist), p(orders_hist), g_reward.t2(), p(dz1), p(dz2),
+                  p(dz3), *mask, _lib.current_stream()))

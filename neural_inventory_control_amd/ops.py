@@ -219,32 +219,45 @@ def linear_models_ok(N, K, n_scenarios, ldb, n_models, wgrad=False):
     return bool(lib().nic_linear_models_ok(int(N), int(K), int(n_scenarios), int(ldb), int(n_models), int(bool(wgrad))))
 
 
-def linear_fwd_models(W, bias, X, Y, n_scenarios, act, bias_stride=None):
+def masked_entry(name, active, n_models):
+    """(the K-model entry point `name` or, with a mask, its `_active` form; what goes between its other arguments and the stream).
+    The kernels read `active[model]` for every grid row: a mask that is not a contiguous int32 [n_models] device tensor is a
+    ValueError here, before anything is launched."""
+    if active is None:
+        return getattr(lib(), name), ()
+    if not active.is_cuda or active.dtype != torch.int32 or tuple(active.shape) != (int(n_models),) or not active.is_contiguous():
+        raise ValueError(f"the active mask must be a contiguous int32 [{int(n_models)}] device tensor, got {active.dtype} {tuple(active.shape)}")
+    return getattr(lib(), name + "_active"), (ptr(active),)
+
+
+def linear_fwd_models(W, bias, X, Y, n_scenarios, act, bias_stride=None, active=None):
     """Y[m] = act(W[m] @ X[m] + bias[m]) for W [M][N][K(ldw)], bias [M][N] (or None; or the first model's [N] with `bias_stride`
-    floats between models), X [M][K][ldb] - or [K][ldb]: one input shared by all models - and Y [M][N][ldb]: one launch."""
+    floats between models), X [M][K][ldb] - or [K][ldb]: one input shared by all models - and Y [M][N][ldb]: one launch.
+    `active` (here and in the two calls below): an int32 [M] device tensor - a model whose entry is zero is skipped, none of its
+    operands read, none of its outputs written (`nic_linear_fwd_models_active`); None: the entry point without a mask."""
     _dev(X)
     M, N = W.shape[0], W.shape[1]
     shared = X.dim() == 2
     K, ldb = X.shape[-2], X.stride(-2)
     if bias is not None and bias_stride is None:
         bias_stride = _model_stride(bias, M, 1)
-    check(lib().nic_linear_fwd_models(ptr(W), _ld(W[0]), _model_stride(W, M, 1), ptr(bias), bias_stride or 0, ptr(X),
-                                      0 if shared else _model_stride(X, M, 1), ptr(Y), _model_stride(Y, M, 1), N, K, n_scenarios,
-                                      ldb, act, M, current_stream()))
+    fn, mask = masked_entry("nic_linear_fwd_models", active, M)
+    check(fn(ptr(W), _ld(W[0]), _model_stride(W, M, 1), ptr(bias), bias_stride or 0, ptr(X), 0 if shared else _model_stride(X, M, 1),
+             ptr(Y), _model_stride(Y, M, 1), N, K, n_scenarios, ldb, act, M, *mask, current_stream()))
     return Y
 
 
-def linear_wgrad_models(dY, X, slab, n_scenarios):
+def linear_wgrad_models(dY, X, slab, n_scenarios, active=None):
     """slab[m][split][N][lds] += per-split sum_b dY[m][N][b] X[m][K][b] (column K = bias gradient): one launch for all models."""
     _dev(dY)
     M, N, K = dY.shape[0], dY.shape[1], X.shape[1]
-    check(lib().nic_linear_wgrad_models(ptr(dY), _model_stride(dY, M, 1), ptr(X), _model_stride(X, M, 1), ptr(slab),
-                                        _model_stride(slab, M, 1), slab.stride(2), N, K, n_scenarios, dY.stride(1), slab.shape[1],
-                                        M, current_stream()))
+    fn, mask = masked_entry("nic_linear_wgrad_models", active, M)
+    check(fn(ptr(dY), _model_stride(dY, M, 1), ptr(X), _model_stride(X, M, 1), ptr(slab), _model_stride(slab, M, 1), slab.stride(2), N, K,
+             n_scenarios, dY.stride(1), slab.shape[1], M, *mask, current_stream()))
     return slab
 
 
-def wgrad_reduce_models(slab, dW, db, K, scale=1.0, dW_stride=None, db_stride=None):
+def wgrad_reduce_models(slab, dW, db, K, scale=1.0, dW_stride=None, db_stride=None, active=None):
     """dW[m][N][lddw] / db[m][N] = scale * the sum over slab[m]'s splits, one launch.  dW [M][N][>= K] and db [M][N] (or None) - or
     model 0's dW [N][>= K] / db [N] with `dW_stride` / `db_stride` floats between models (rows of a packed gradient buffer)."""
     M = slab.shape[0]
@@ -253,8 +266,9 @@ def wgrad_reduce_models(slab, dW, db, K, scale=1.0, dW_stride=None, db_stride=No
     if db is not None and db_stride is None:
         db_stride, db = _model_stride(db, M, 1), db[0]
     N = dW.shape[0]
-    check(lib().nic_wgrad_reduce_models(ptr(slab), _model_stride(slab, M, 1), slab.stride(2), slab.shape[1], ptr(dW), _ld(dW),
-                                        dW_stride, ptr(db), db_stride or 0, N, K, float(scale), M, current_stream()))
+    fn, mask = masked_entry("nic_wgrad_reduce_models", active, M)
+    check(fn(ptr(slab), _model_stride(slab, M, 1), slab.stride(2), slab.shape[1], ptr(dW), _ld(dW), dW_stride, ptr(db), db_stride or 0,
+             N, K, float(scale), M, *mask, current_stream()))
 
 
 # ---- policy heads ----------------------------------------------------------------------------------------------
